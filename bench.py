@@ -30,8 +30,13 @@ Besides the driver contract fields the JSON line carries the multi-GPU diagnosti
 ``dist`` (backend and world size as every rank saw them), ``bucket_plan`` (count / sizes of the
 gradient buckets), ``comm_exposed_ms`` (non-overlapped gradient-collective wait per step, max over
 ranks), per-rank ``peak_mem_gb`` / ``ms_per_step`` and, given ``--baseline-1gpu V``,
-``scaling_efficiency = value / (N * V)``. ``comm_probe`` (N > 1, measured between warmup and the timed steps):
-reduce-scatter / all-gather / all-reduce bus bandwidth at the bucket size, i.e. what xGMI delivered on that node.
+``scaling_efficiency = value / (N * V)``. ``comm_probe`` (``--full`` at N > 1, measured between warmup and the timed
+steps): reduce-scatter / all-gather / all-reduce bus bandwidth at the bucket size, i.e. what xGMI delivered on that node.
+
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` optimizer steps, print the JSON
+line. Measurements of their own (today: ``comm_probe``) run only with ``--full``. ``--dump-outputs DIR`` writes what the
+last timed step computed (``dump_outputs`` below) before the JSON line is printed; model, data and the stochastic-rounding
+seeds are fixed, so with the same arguments two runs start from identical inputs.
 """
 from __future__ import annotations
 
@@ -110,7 +115,15 @@ def parse(argv=None):
                     help="seconds without progress (no heartbeat) before a rank is declared hung")
     ap.add_argument("--no-rccl-info", action="store_true", help="N > 1: do not capture RCCL's INFO log")
     ap.add_argument("--rccl-log-dir", default="/tmp/sftamd_rccl")
-    ap.add_argument("--no-comm-probe", action="store_true", help="N > 1: skip the post-warmup collective probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: at N > 1 the post-warmup collective probe "
+                         "(comm_probe in the JSON line). Off by default: a plain run sets up, warms up, times the "
+                         "steps and prints the result line")
+    ap.add_argument("--no-comm-probe", action="store_true", help="--full at N > 1: skip the collective probe anyway")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last of them computed to DIR/<name>.npy (float32): "
+                         "acc and grad_norm as optimizer_step returned them, params = the parameters it left behind "
+                         "(a fixed seeded sample when the model is larger than the sample)")
     ap.add_argument("--no-strict-dist", action="store_true",
                     help="N > 1 on GPUs: still exit 0 when RCCL's log shows a degraded path (non-P2P transport, rank "
                          "count mismatch, failed init, fewer channels than peer links); by default the JSON line is "
@@ -173,6 +186,27 @@ def comm_probe(dev, world: int, nbytes: int, iters: int = 5) -> dict:
         out[f"{name}_ms"] = round(dt * 1e3, 3)
         out[f"{name}_busbw_gbps"] = round(bus / 1e9, 1)
     return out
+
+
+DUMP_PARAM_SAMPLE = 1 << 22  # parameters kept by --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(out_dir: str, result: dict, param_flat) -> None:
+    """``--dump-outputs``: what the last timed ``optimizer_step`` handed its caller, one float32 ``.npy`` each: the
+    sums it returned (``acc``: this rank's loss share, correct, entropy_sum, valid tokens), the gradient norm it
+    returned (``grad_norm``) and the parameters it left behind (``params``: the flat parameter buffer, or, when that is
+    larger than DUMP_PARAM_SAMPLE, its elements at DUMP_PARAM_SAMPLE sorted indices drawn with a fixed seed: the same
+    elements in every run, so two builds compare element for element)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = param_flat.detach().reshape(-1)
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0))
+        flat = flat[idx.sort().values.to(flat.device)]
+    for name, t in (("acc", result["acc"]), ("grad_norm", result["grad_norm"]), ("params", flat)):
+        np.save(os.path.join(out_dir, name + ".npy"),
+                torch.as_tensor(t).detach().to(device="cpu", dtype=torch.float32).reshape(-1).numpy())
 
 
 def run(a):
@@ -262,7 +296,7 @@ def run(a):
     sync()
     beat(None, "warmup_done")
     probe = None
-    if st.world_size > 1 and not a.no_comm_probe:
+    if a.full and st.world_size > 1 and not a.no_comm_probe:
         probe = comm_probe(st.device, st.world_size, int(trainer.engine.bucket_cap_mb * 2 ** 20))
     barrier()
     sync()
@@ -277,7 +311,9 @@ def run(a):
     dt = time.perf_counter() - t0
     comm_ms = trainer.engine.comm_exposed_ms(reset=True)
     beat(None, "timed_done")
-    peak = torch.cuda.max_memory_allocated() / 1e9 if on_gpu else 0.0
+    if a.dump_outputs and st.is_main:
+        dump_outputs(a.dump_outputs, r, trainer.engine.param_flat)
+    peak =torch.cuda.max_memory_allocated() / 1e9 if on_gpu else 0.0
     mine = {"rank": st.rank, "world_size": dist.get_world_size() if dist.is_initialized() else 1,
             "backend": dist.get_backend() if dist.is_initialized() else None,
             "device": str(st.device), "ms_per_step": round(dt / a.steps * 1e3, 3), "peak_mem_gb": round(peak, 2),
@@ -484,6 +520,8 @@ def _sum_key(x: float):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
+    if a.recipe and a.dump_outputs:
+        raise SystemExit("--dump-outputs belongs to the synthetic step loop, not to --recipe")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a, argv))
     if a.recipe:

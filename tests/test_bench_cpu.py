@@ -58,8 +58,39 @@ def test_bench_self_launches_n_ranks(n):
     else:
         assert rec["bucket_plan"]["plan_source"] == "model" and rec["dist"]["link_probe"] == []
     assert rec["bucket_plan"]["count"] >= 1
+    assert rec["comm_probe"] is None  # a plain run measures its steps only; the collective probe needs --full
     assert rec["scaling_efficiency"] == pytest.approx(rec["value"] / (n * 10), rel=1e-3)
     assert rec["value"] > 0 and rec["final_loss"] > 0
+
+
+def test_bench_full_runs_the_collective_probe():
+    r = _bench(2, ["--full"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    probe = _json_lines(r.stdout)[0]["comm_probe"]
+    for k in ("reduce_scatter", "all_gather", "all_reduce"):
+        assert probe[f"{k}_ms"] > 0 and probe[f"{k}_busbw_gbps"] >= 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes what the last timed optimizer step returned (acc, grad_norm) and left behind (params) as
+    float32 .npy files; with the same arguments a second run starts from the same inputs and writes the same values."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench(1, ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json_lines(r.stdout)[0]
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["acc.npy", "grad_norm.npy", "params.npy"]
+        out = {k: np.load(tmp_path / d / f"{k}.npy") for k in ("acc", "grad_norm", "params")}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+        assert out["acc"].shape == (4,) and out["grad_norm"].shape == (1,) and out["params"].size > 1000
+        assert out["acc"][0] == pytest.approx(rec["final_loss"], abs=1e-4)  # the loss the JSON line reports
+        assert out["acc"][3] == 2 * 31  # valid tokens of the step: micro-batch 2 x (seq 32 - 1) shifted labels
+        assert sum(v.nbytes for v in out.values()) <= 64 * 2 ** 20
+        dumps.append(out)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[0][k], dumps[1][k], rtol=1e-5, atol=1e-6, err_msg=k)
 
 
 def test_bench_replicated_ddp_path():

@@ -89,10 +89,9 @@ def test_template_helpers_behave_like_hf(tpl):
                                                                                  "eos_token": "</s>"}) == "<s>|</s>"
 
 
-REF_PARQUET = "/root/reference/data/qa_dataset.parquet"
+REF_PARQUET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "qa_dataset.parquet")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PARQUET), reason="reference dataset not present")
 def test_reference_rows_token_counts(tpl):
     """Token counts of the reference's own parquet rows through both template paths (synthetic BPE
     tokenizer: the real SmolLM3 vocabulary is not available offline, so absolute counts are unpinned)."""
