@@ -151,7 +151,19 @@ at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor&
     const long bpc = std::max(1L, std::min(8L, (200L << 20) / ((long)num_cus() * row_bytes)));
     if (bpc < 8) pad = (int)((160L * 1024) / bpc - 1024);
   }
-    ce_fwd_kernel<4><<<M, 256, pad, cur_stream()>>>(lg, lab.data_ptr<int64_t>(), inv_count.data_ptr<float>(),
+  // The pad passes 64 KB once bpc drops to 2 (V above ~136K: 79 KB at 151,936, 159 KB at 262,144), and a launch above
+  // 64 KB of dynamic LDS needs the limit raised first (cu_hog does the same for its 81 KB). Raised once to the largest
+  // pad, bpc = 1: with the kernel's static reduction scratch (under 1 KB) the block stays within the CU's 160 KB.
+  constexpr int kMaxPad = 160 * 1024 - 1024;
+  if (pad > 64 * 1024) {
+    static bool attr = [] {
+      return hipFuncSetAttribute((const void*)ce_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxPad) ==
+             hipSuccess;
+    }();
+    SFT_CHECK(attr, "ce_fwd: could not raise the dynamic LDS limit");
+  }
+  SFT_CHECK(pad <= kMaxPad, "ce_fwd: LDS pad over the CU's 160 KB");
+  ce_fwd_kernel<4><<<M, 256, pad, cur_stream()>>>(lg, lab.data_ptr<int64_t>(), inv_count.data_ptr<float>(),
                                                   stats.data_ptr<float>(), M, V, write_grad ? 1 : 0);
   SFT_LAUNCH_CHECK();
   return stats;

@@ -172,7 +172,8 @@ __device__ __forceinline__ void gather8(const f32x4 (&acc)[8][8], int i, int p, 
   }
 }
 
-// Whole tile -> C (bf16, optionally + C); nrm: this wave's gradient-norm slot (sum of squares of the stored values).
+// Whole tile -> C (bf16, optionally + C); nrm: this wave's gradient-norm slot (sum of squares of the fp32 values it
+// stores, before the bf16 rounding, as the 8-wave rings do; the split-K fixup squares the stored bf16).
 __device__ __forceinline__ void store_tile(const f32x4 (&acc)[8][8], const Epi& ea, int row0, int col0, int lane,
                                            float* nrm) {
   const int g = lane >> 4, ii = lane & 15;

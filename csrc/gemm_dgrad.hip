@@ -555,10 +555,12 @@ std::tuple<at::Tensor, at::Tensor> dgrad_gemm_delta(const at::Tensor& dy, const 
 }
 
 // dX = dy @ w (w [K, N]); with gate_up ([M, 2N], the SwiGLU input saved by the forward) the SwiGLU backward
-// is fused: returns dgu [M, 2N] instead of dX. cfg: 14 = the 4-wave ring (csrc/gemm_4w.hip; every plain SmolLM3 /
-// Llama dgrad), 7 = 256 x 256 tiles with 64-deep stages (the SwiGLU-backward epilogue: 0.425 vs 0.483 ms for the
-// 4-wave kernel's register epilogue, profiles/r6_gemm_routing.md), 5 = the 32-deep ring (K % 64 != 0), 2 = 256 x 128
-// tiles (the wave-tail launch below).
+// is fused: returns dgu [M, 2N] instead of dX. cfg, as _dgrad_cfg (ops/fused.py) routes them: 5 = the 8-wave 32-deep
+// ring — every SwiGLU-fused dgrad (0.400 vs 0.409 ms for cfg 7 and 0.483 for the 4-wave kernel's register epilogue,
+// profiles/r6_gemm_routing.md), plain dgrads with K % 128 == 0 whose grid is whole rounds of 256 CUs or takes the
+// wave-tail launch below, and K % 64 != 0; 14 = the 4-wave ring (csrc/gemm_4w.hip, plain epilogue only): K % 128 == 0
+// on ragged grids (its split-K tail) and vocabulary-long reductions (lm_head); 7 = 256 x 256 tiles with 64-deep
+// stages: K % 128 != 0 with K % 64 == 0; 2 = 256 x 128 tiles (the wave-tail launch below, never routed on its own).
 at::Tensor dgrad_gemm(const at::Tensor& dy, const at::Tensor& w, const c10::optional<at::Tensor>& gate_up,
                       int64_t cfg) {
   SFT_CHECK_CUDA(dy);

@@ -7,6 +7,8 @@ import torch
 
 from llm_fine_tune_distributed_amd.ops import _ext
 
+from _blockwise import assert_blocks_close, rounding_floor, swiglu_bwd_reference
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -138,10 +140,14 @@ def test_dgrad_4wave_wave_tail(swiglu, cfg, monkeypatch):
         want = torch.cat([dact * u * s * (1 + g * (1 - s)), dact * g * s], dim=-1)
     else:
         want = dact
+    dact64 = dy.double() @ w.double()
+    want64, bound = swiglu_bwd_reference(dact64, gu) if swiglu else (dact64, 2 * rounding_floor(dact64, 32, 32))
     for tail in ("0", "2"):
         monkeypatch.setenv("SFTAMD_DGRAD_TAIL", tail)
         got = _ext.ops().dgrad_gemm(dy, w, gu, cfg)
         assert rel_err(got, want) < 1e-2, tail
+        worst = assert_blocks_close(got, want64, 32, 32, bound, f"dgrad cfg {cfg} swiglu={swiglu} tail={tail}")
+        print(f"dgrad_4wave_wave_tail cfg {cfg} swiglu={swiglu} tail={tail}: worst 32x32 block {worst:.3e}, bound {bound:.3e}")
 
 
 @pytest.mark.parametrize("cfg", [14])
@@ -278,6 +284,11 @@ def test_wgrad_pair_one_launch(N0, K0, N1, K1, T, accumulate):
         assert (w1 != r1).float().mean().item() < 0.05  # only the split leftover tiles may differ
     want = (dy1.float().t() @ x1.float()) + (base1.float() if accumulate else 0)
     assert rel_err(w1, want) < 5e-3
+    for o, dy, x, b in ((w0, dy0, x0, base0), (w1, dy1, x1, base1)):  # every 32 x 32 block, the split leftover tiles too
+        want64 = dy.double().t() @ x.double() + (b.double() if accumulate else 0)
+        floor = rounding_floor(want64, 32, 32)
+        worst = assert_blocks_close(o, want64, 32, 32, 2 * floor, f"wgrad pair {tuple(o.shape)}")
+        print(f"wgrad_pair T={T} {tuple(o.shape)} acc={accumulate}: worst 32x32 block {worst:.3e}, rounding floor {floor:.3e}")
     assert abs(n0.sum().item() - w0.float().pow(2).sum().item()) < 1e-3 * w0.float().pow(2).sum().item()
     assert abs(n1.sum().item() - w1.float().pow(2).sum().item()) < 1e-3 * w1.float().pow(2).sum().item()
     v0, v1 = base0.clone(), base1.clone()
@@ -346,6 +357,12 @@ def test_wgrad_multi_four_problems(accumulate, split_left):
     for o, dy, x, b, nr in zip(outs, dys, xs, bases, norms):
         want = dy.float().t() @ x.float() + (b.float() if accumulate else 0)
         assert rel_err(o, want) < 5e-3
+        want64 = dy.double().t() @ x.double() + (b.double() if accumulate else 0)
+        floor = rounding_floor(want64, 32, 32)
+        worst = assert_blocks_close(o, want64, 32, 32, 2 * floor, f"wgrad multi {tuple(o.shape)}")
+        print(f"wgrad_multi {tuple(o.shape)} acc={accumulate} split_left={split_left}: worst 32x32 block {worst:.3e}, "
+              f"rounding floor {floor:.3e}")
+        del want64
         ref = o.float().pow(2).sum().item()
         assert abs(nr.sum().item() - ref) < 1e-3 * ref
     # down (problem 0) lies wholly in the 4 whole rounds: bitwise the single cfg-14 launch

@@ -9,6 +9,8 @@ import torch
 from llm_fine_tune_distributed_amd.ops import _ext
 from llm_fine_tune_distributed_amd.ops import reference as ref
 
+from _blockwise import assert_blocks_close, rounding_floor, swiglu_bwd_reference
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -611,6 +613,10 @@ def test_gemm_tn_plain(cfg, M, N, K):
     w = torch.randn(N, K, device=DEV, dtype=torch.bfloat16)
     c = _ext.ops().gemm_tn(x, w, cfg)
     assert rel_err(c, x.float() @ w.float().t()) < 5e-3
+    want64 = x.double() @ w.double().t()  # every 32 x 32 block on its own: within twice the output rounding
+    floor = rounding_floor(want64, 32, 32)
+    worst = assert_blocks_close(c, want64, 32, 32, 2 * floor, f"gemm_tn cfg {cfg}")
+    print(f"gemm_tn_plain cfg {cfg} {M}x{N}x{K}: worst 32x32 block {worst:.3e}, rounding floor {floor:.3e}")
 
 
 def _elem_ok(out, exp, tol=1e-2):
@@ -761,6 +767,11 @@ def test_dgrad_gemm_wave_tail_split(M, K, N, swiglu, monkeypatch):
     else:
         want = dact
     assert rel_err(res["2"], want) < 1e-2
+    # every 32 x 32 block on its own (the leftover columns of the tail launch are 3 of 43 column tiles)
+    dact64 = dy.double() @ w.double()
+    want64, bound = swiglu_bwd_reference(dact64, gu) if swiglu else (dact64, 2 * rounding_floor(dact64, 32, 32))
+    worst = assert_blocks_close(res["2"], want64, 32, 32, bound, f"dgrad wave tail {M}x{K}x{N} swiglu={swiglu}")
+    print(f"dgrad_wave_tail_split {M}x{K}x{N} swiglu={swiglu}: worst 32x32 block {worst:.3e}, bound {bound:.3e}")
 
 
 @pytest.mark.parametrize("M,K,N", [(256, 256, 256), (512, 2048, 512), (256, 64, 768), (2048, 2048, 2816)])
@@ -780,3 +791,6 @@ def test_dgrad_gemm_swiglu_bwd(M, K, N):
     want = torch.cat([dact * u * s * (1 + g * (1 - s)), dact * g * s], dim=-1)
     assert dgu.shape == (M, 2 * N)
     assert rel_err(dgu, want) < 1e-2, rel_err(dgu, want)
+    want64, bound = swiglu_bwd_reference(dy.double() @ w.double(), gu)
+    worst = assert_blocks_close(dgu, want64, 32, 32, bound, f"dgrad swiglu {M}x{K}x{N}")
+    print(f"dgrad_swiglu_bwd {M}x{K}x{N}: worst 32x32 block {worst:.3e}, bound {bound:.3e}")
