@@ -83,8 +83,10 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None) -> Tensor");
   m.def("flash_bwd_rope(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor cos, Tensor sin, Tensor? delta=None) -> Tensor");
   m.def("decode_attention(Tensor q, Tensor kcache, Tensor vcache, Tensor cache_len, int n_q, int n_kv, float scale) -> Tensor");
+  m.def("decode_attention_batched(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor lens, int n_q, int n_kv, float scale) -> Tensor");
   // fused decode sampler: penalty -> temperature -> top-k -> top-p -> draw, device-resident state
   m.def("sample_token(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");
+  m.def("sample_tokens(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, Tensor(g!) done, int eos_token_id, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");
   // weight-gradient GEMM: out[N,K] (+)= dy[T,N]^T x[T,K]
   m.def("wgrad_gemm(Tensor(a!) out, Tensor dy, Tensor x, bool accumulate, int cfg=14, Tensor(b!)? norm=None) -> ()");
   m.def("wgrad_gemm_multi(Tensor(a!)[] outs, Tensor[] dys, Tensor[] xs, int[] accs, Tensor(b!)[] norms, int split_all=0, int split_left=0) -> ()");

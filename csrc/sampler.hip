@@ -14,6 +14,8 @@
 //            counter, so every graph replay draws fresh). It writes the token to the next step's
 //            embedding input, to a device token log, sets the token's presence bit and advances the
 //            counters (position, KV length, step) — the decode loop runs replay after replay.
+// sample_tokens is the same pair of launches for B rows (grid (tiles, B), then one merge block per row) with a
+// per-row finished flag: batched generation decodes many prompts per step.
 #include "common.h"
 
 #include <rocprim/block/block_radix_sort.hpp>
@@ -34,16 +36,18 @@ __device__ __forceinline__ float to_f<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ float to_f<u16>(u16 v) { return bf2f(v); }
 
+// One 2048-logit tile of one row (shared by the single-row and the batched kernel): logits / presence / cand_* point
+// at the row, ``tile`` is the tile's index within it.
 template <typename T>
-__global__ __launch_bounds__(NT) void partial_kernel(const T* __restrict__ logits, int V,
-                                                     const unsigned* __restrict__ presence, float inv_temp,
-                                                     float penalty, int K, float* __restrict__ cand_v,
-                                                     int* __restrict__ cand_i) {
+__device__ __forceinline__ void partial_body(const T* __restrict__ logits, int V,
+                                             const unsigned* __restrict__ presence, float inv_temp, float penalty,
+                                             int K, float* __restrict__ cand_v, int* __restrict__ cand_i,
+                                             const int tile) {
   using Sort = rocprim::block_radix_sort<float, NT, IPT, int>;
   __shared__ typename Sort::storage_type storage;
   float key[IPT];
   int idx[IPT];
-  const int base = blockIdx.x * TILE;
+  const int base = tile * TILE;
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
     const int i = base + j * NT + threadIdx.x;  // striped loads: coalesced
@@ -61,19 +65,44 @@ __global__ __launch_bounds__(NT) void partial_kernel(const T* __restrict__ logit
   for (int j = 0; j < IPT; ++j) {
     const int r = threadIdx.x * IPT + j;
     if (r < K) {
-      cand_v[blockIdx.x * K + r] = key[j];
-      cand_i[blockIdx.x * K + r] = idx[j];
+      cand_v[tile * K + r] = key[j];
+      cand_i[tile * K + r] = idx[j];
     }
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(NT) void partial_kernel(const T* __restrict__ logits, int V,
+                                                     const unsigned* __restrict__ presence, float inv_temp,
+                                                     float penalty, int K, float* __restrict__ cand_v,
+                                                     int* __restrict__ cand_i) {
+  partial_body<T>(logits, V, presence, inv_temp, penalty, K, cand_v, cand_i, blockIdx.x);
+}
+
+// grid (tiles, B): logits [B, V], presence [B, words], cand_* [B, tiles * K]. A finished row is skipped.
+template <typename T>
+__global__ __launch_bounds__(NT) void partial_batched_kernel(const T* __restrict__ logits, int V,
+                                                             const unsigned* __restrict__ presence, int words,
+                                                             float inv_temp, float penalty, int K,
+                                                             float* __restrict__ cand_v, int* __restrict__ cand_i,
+                                                             const int* __restrict__ done) {
+  const int b = blockIdx.y;
+  if (done[b]) return;
+  const long nc = (long)gridDim.x * K;
+  partial_body<T>(logits + (long)b * V, V, presence + (long)b * words, inv_temp, penalty, K, cand_v + b * nc,
+                  cand_i + b * nc, blockIdx.x);
+}
+
+// The merge + draw of one row (shared by the single-row and the batched kernel); every pointer is the row's own.
+// ``done`` (batched only, else null) is the row's finished flag: drawing ``eos`` logs the token, sets the flag and
+// leaves position / KV length where they are (the EOS is never decoded).
 // state (int64): [0] step counter (RNG), [1] last token, [2] position, [3] KV length (int64 mirror)
-__global__ __launch_bounds__(NT) void final_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                   int ncand, int K, float top_p, int do_sample, unsigned seed,
-                                                   long long* __restrict__ state, long long* __restrict__ tok_out,
-                                                   long long* __restrict__ pos_out, int* __restrict__ len_out,
-                                                   long long* __restrict__ log, int log_cap,
-                                                   unsigned* __restrict__ presence) {
+__device__ __forceinline__ void final_body(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                           int ncand, int K, float top_p, int do_sample, unsigned seed,
+                                           long long* __restrict__ state, long long* __restrict__ tok_out,
+                                           long long* __restrict__ pos_out, int* __restrict__ len_out,
+                                           long long* __restrict__ log, int log_cap, unsigned* __restrict__ presence,
+                                           int* __restrict__ done, int eos) {
   using Sort = rocprim::block_radix_sort<float, NT, IPT2, int>;
   __shared__ typename Sort::storage_type storage;
   __shared__ float top_v[KMAX];
@@ -128,7 +157,9 @@ __global__ __launch_bounds__(NT) void final_kernel(const float* __restrict__ can
   state[1] = tok;
   if (tok_out) tok_out[0] = tok;
   if (log && step < log_cap) log[step] = tok;
-  if (pos_out) {  // advance the decode step's position / KV length for the next replay
+  const bool finished = done != nullptr && tok == eos;
+  if (finished) *done = 1;
+  if (pos_out && !finished) {  // advance the decode step's position / KV length for the next replay
     const long long p = state[2] + 1;
     state[2] = p;
     pos_out[0] = p;
@@ -136,6 +167,34 @@ __global__ __launch_bounds__(NT) void final_kernel(const float* __restrict__ can
     len_out[0] = (int)(p + 1);
   }
   atomicOr(presence + (tok >> 5), 1u << (tok & 31));
+}
+
+__global__ __launch_bounds__(NT) void final_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                   int ncand, int K, float top_p, int do_sample, unsigned seed,
+                                                   long long* __restrict__ state, long long* __restrict__ tok_out,
+                                                   long long* __restrict__ pos_out, int* __restrict__ len_out,
+                                                   long long* __restrict__ log, int log_cap,
+                                                   unsigned* __restrict__ presence) {
+  final_body(cand_v, cand_i, ncand, K, top_p, do_sample, seed, state, tok_out, pos_out, len_out, log, log_cap,
+             presence, nullptr, -1);
+}
+
+// One block per row; row b draws with seed + b. A finished row writes nothing at all.
+__global__ __launch_bounds__(NT) void final_batched_kernel(const float* __restrict__ cand_v,
+                                                           const int* __restrict__ cand_i, int ncand, int K,
+                                                           float top_p, int do_sample, unsigned seed,
+                                                           long long* __restrict__ state,
+                                                           long long* __restrict__ tok_out,
+                                                           long long* __restrict__ pos_out, int* __restrict__ len_out,
+                                                           long long* __restrict__ log, int log_cap,
+                                                           unsigned* __restrict__ presence, int words,
+                                                           int* __restrict__ done, int eos) {
+  const int b = blockIdx.x;
+  if (done[b]) return;
+  final_body(cand_v + (long)b * ncand, cand_i + (long)b * ncand, ncand, K, top_p, do_sample, seed + (unsigned)b,
+             state + b * 4, tok_out ? tok_out + b : nullptr, pos_out ? pos_out + b : nullptr,
+             len_out ? len_out + b : nullptr, log ? log + (long)b * log_cap : nullptr, log_cap,
+             presence + (long)b * words, done + b, eos);
 }
 
 }  // namespace samp
@@ -181,6 +240,66 @@ void sample_token(const at::Tensor& logits, at::Tensor presence, at::Tensor stat
   SFT_LAUNCH_CHECK();
 }
 
-TORCH_LIBRARY_IMPL(sftamd, CUDA, m) { m.impl("sample_token", &sample_token); }
+// B rows at once: logits [B, V] (bf16 or fp32), presence int32 [B, >= ceil(V/32)], state int64 [B, 4], done int32 [B];
+// tok_out / pos_out int64 [B], len_out int32 [B] and log int64 [B, cap] are optional. Row b applies sample_token's
+// rules with seed + b, so row 0 reproduces sample_token with the same seed. A row that draws eos_token_id (-1: none)
+// logs it and sets done[b]; a row whose done[b] is set is skipped entirely.
+void sample_tokens(const at::Tensor& logits, at::Tensor presence, at::Tensor state, const c10::optional<at::Tensor>& tok_out,
+                   const c10::optional<at::Tensor>& pos_out, const c10::optional<at::Tensor>& len_out,
+                   const c10::optional<at::Tensor>& log, at::Tensor done, int64_t eos_token_id, double temperature,
+                   int64_t top_k, double top_p, double repetition_penalty, bool do_sample, int64_t seed) {
+  SFT_CHECK_CUDA(logits);
+  SFT_CHECK(logits.dim() == 2 && logits.is_contiguous() &&
+                (logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16),
+            "sample_tokens: contiguous fp32/bf16 logits [B, V]");
+  const int64_t B = logits.size(0);
+  const int V = logits.size(1);
+  SFT_CHECK(B >= 1 && B <= 65535 && V >= 1, "sample_tokens: batch size");
+  SFT_CHECK(presence.is_cuda() && presence.scalar_type() == at::kInt && presence.dim() == 2 && presence.size(0) == B &&
+                presence.size(1) >= (V + 31) / 32 && presence.is_contiguous(),
+            "sample_tokens: presence int32 bitmask [B, ceil(V/32)]");
+  SFT_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.dim() == 2 && state.size(0) == B &&
+                state.size(1) == 4 && state.is_contiguous(), "sample_tokens: state int64 [B, 4]");
+  SFT_CHECK(done.is_cuda() && done.scalar_type() == at::kInt && done.numel() == B && done.is_contiguous(),
+            "sample_tokens: done int32 [B]");
+  const int K = do_sample ? (int)top_k : 1;
+  SFT_CHECK(K >= 1 && K <= samp::KMAX && K <= V, "sample_tokens: top_k must be in [1, min(64, V)] on the device path");
+  const int nblk = (V + samp::TILE - 1) / samp::TILE;
+  SFT_CHECK(nblk * K <= samp::NT * samp::IPT2, "sample_tokens: vocabulary too large for one merge block");
+  SFT_CHECK(!tok_out.has_value() || (tok_out->is_cuda() && tok_out->scalar_type() == at::kLong &&
+                                     tok_out->numel() == B && tok_out->is_contiguous()), "sample_tokens: tok int64 [B]");
+  SFT_CHECK(!pos_out.has_value() ||
+                (len_out.has_value() && pos_out->is_cuda() && len_out->is_cuda() && pos_out->scalar_type() == at::kLong &&
+                 len_out->scalar_type() == at::kInt && pos_out->numel() == B && len_out->numel() == B &&
+                 pos_out->is_contiguous() && len_out->is_contiguous()), "sample_tokens: pos int64 [B] / len int32 [B]");
+  SFT_CHECK(!log.has_value() || (log->is_cuda() && log->scalar_type() == at::kLong && log->dim() == 2 &&
+                                 log->size(0) == B && log->is_contiguous()), "sample_tokens: log int64 [B, cap]");
+  auto cv = at::empty({B * nblk * K}, logits.options().dtype(at::kFloat));
+  auto ci = at::empty({B * nblk * K}, logits.options().dtype(at::kInt));
+  const float inv_t = do_sample ? (float)(1.0 / std::max(temperature, 1e-5)) : 1.f;
+  const int words = presence.size(1);
+  if (logits.scalar_type() == at::kFloat)
+    samp::partial_batched_kernel<float><<<dim3(nblk, B), samp::NT, 0, cur_stream()>>>(
+        logits.data_ptr<float>(), V, (const unsigned*)presence.data_ptr<int>(), words, inv_t,
+        (float)repetition_penalty, K, cv.data_ptr<float>(), ci.data_ptr<int>(), done.data_ptr<int>());
+  else
+    samp::partial_batched_kernel<u16><<<dim3(nblk, B), samp::NT, 0, cur_stream()>>>(
+        (const u16*)logits.data_ptr(), V, (const unsigned*)presence.data_ptr<int>(), words, inv_t,
+        (float)repetition_penalty, K, cv.data_ptr<float>(), ci.data_ptr<int>(), done.data_ptr<int>());
+  SFT_LAUNCH_CHECK();
+  samp::final_batched_kernel<<<B, samp::NT, 0, cur_stream()>>>(
+      cv.data_ptr<float>(), ci.data_ptr<int>(), nblk * K, K, (float)top_p, do_sample ? 1 : 0, (unsigned)seed,
+      (long long*)state.data_ptr<int64_t>(), tok_out.has_value() ? (long long*)tok_out->data_ptr<int64_t>() : nullptr,
+      pos_out.has_value() ? (long long*)pos_out->data_ptr<int64_t>() : nullptr,
+      len_out.has_value() ? len_out->data_ptr<int>() : nullptr,
+      log.has_value() ? (long long*)log->data_ptr<int64_t>() : nullptr, log.has_value() ? (int)log->size(1) : 0,
+      (unsigned*)presence.data_ptr<int>(), words, done.data_ptr<int>(), (int)eos_token_id);
+  SFT_LAUNCH_CHECK();
+}
+
+TORCH_LIBRARY_IMPL(sftamd, CUDA, m) {
+  m.impl("sample_token", &sample_token);
+  m.impl("sample_tokens", &sample_tokens);
+}
 
 }  // namespace sftamd

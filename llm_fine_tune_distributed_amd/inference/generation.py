@@ -9,6 +9,11 @@ length from device memory — so ONE decode step is captured into a hipGraph and
 token (no per-layer launch overhead, no host sync inside the step). On CPU the same step runs
 eagerly. Sampling matches HF's logits-processor order: repetition penalty -> temperature ->
 top-k -> top-p -> multinomial.
+
+``generate_batch`` decodes many prompts per step: one packed varlen prefill, one cache slab per
+sequence (``BatchKVCache``), and a ``BatchGraphDecoder`` whose captured step runs B rows through
+the batched decode attention and the batched sampler, so the weights are read once per step for
+the whole batch. Element b of its result is what ``generate`` returns for prompt b with seed + b.
 """
 from __future__ import annotations
 
@@ -281,3 +286,246 @@ def _generate_device(model, dec: GraphDecoder, cache: KVCache, prompt_ids, logit
         done += n
     cache.len = len(prompt_ids) + len(out)
     return out
+
+
+# ----------------------------------------------------------------------------- batched generation
+class BatchKVCache:
+    """One slab [S_max, nkv, D] per sequence and layer: ``k[li]`` is the [B, S_max, nkv, D] cache of layer li.
+    ``lens[b]`` is the number of tokens of sequence b already in the cache."""
+
+    def __init__(self, cfg, batch: int, max_len: int, device, dtype=torch.bfloat16):
+        L = cfg.num_hidden_layers
+        self.k = torch.empty(L, batch, max_len, cfg.num_key_value_heads, cfg.head_dim, device=device, dtype=dtype)
+        self.v = torch.empty_like(self.k)
+        self.lens = [0] * batch
+
+
+@torch.no_grad()
+def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch.Tensor:
+    """All prompts in ONE packed varlen pass (cu_seqlens, per-sample positions) through the ops forward_cached
+    uses; K/V are scattered into each sequence's slab. Returns the last-token logits [B, V] (fp32)."""
+    cfg = model.config
+    dev = model.model.embed_tokens.device
+    nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+    n = [len(p) for p in prompts]
+    assert len(n) == len(cache.lens) and min(n) > 0 and max(n) <= cache.k.shape[2], "prompts do not fit the cache"
+    ids = torch.tensor([t for p in prompts for t in p], device=dev)
+    bounds = [0]
+    for x in n:
+        bounds.append(bounds[-1] + x)
+    cu = torch.tensor(bounds, dtype=torch.int32, device=dev)
+    pos = torch.cat([torch.arange(x) for x in n]).to(dev)
+    seq = torch.repeat_interleave(torch.arange(len(n)), torch.tensor(n)).to(dev)
+    M = ids.numel()
+    x = ops.embedding(ids, model.model.embed_tokens)
+    residual = None
+    cos = sin = None
+    for li, layer in enumerate(model.model.layers):
+        at = layer.self_attn
+        h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
+        qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
+        if at.use_rope:
+            if cos is None:
+                cos, sin = model.rope_tables(pos)
+            ops.rope_(qkv, cos, sin, nq, nkv, D)
+        cache.k[li][seq, pos] = qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D)
+        cache.v[li][seq, pos] = qkv[:, (nq + nkv) * D:].view(M, nkv, D)
+        a = ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D)
+        o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
+        h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
+        x = layer.mlp(h)
+    cache.lens = list(n)
+    last = (cu[1:] - 1).long()
+    h, _ = ops.add_rms_norm(x[last], residual[last], model.model.norm.weight, cfg.rms_norm_eps)
+    return torch.nn.functional.linear(h, model.lm_head_weight).float()
+
+
+class BatchDeviceSampler:
+    """DeviceSampler for B rows (``sample_tokens`` in csrc/sampler.hip): presence [B, words], state [B, 4],
+    log [B, cap] and a ``done`` flag per row. Row b draws with ``seed + b``; a row that draws EOS logs it, sets its
+    flag and is skipped from then on."""
+
+    def __init__(self, vocab_size: int, device, histories, max_new_tokens: int, seed: Optional[int],
+                 eos_token_id: Optional[int], temperature: float, top_k: int, top_p: Optional[float],
+                 repetition_penalty: float, do_sample: bool):
+        import numpy as np
+        B = len(histories)
+        words = np.zeros((B, (vocab_size + 31) // 32), dtype=np.uint32)
+        for b, hist in enumerate(histories):
+            ids = np.asarray(list(hist), dtype=np.int64)
+            np.bitwise_or.at(words[b], ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+        self.presence = torch.from_numpy(words.view(np.int32).copy()).to(device)
+        self.state = torch.zeros(B, 4, dtype=torch.long, device=device)
+        self.log = torch.full((B, max(1, max_new_tokens)), -1, dtype=torch.long, device=device)
+        self.done = torch.zeros(B, dtype=torch.int32, device=device)
+        self.eos = -1 if eos_token_id is None else int(eos_token_id)
+        self.params = (float(temperature), int(top_k) if do_sample else 1, float(top_p if top_p is not None else 1.0),
+                       float(repetition_penalty or 1.0), bool(do_sample),
+                       int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+
+    def sample(self, logits: torch.Tensor, tok_out=None, pos_out=None, len_out=None) -> None:
+        t, k, p, rp, ds, seed = self.params
+        ops_ext().sample_tokens(logits.contiguous(), self.presence, self.state, tok_out, pos_out, len_out, self.log,
+                                self.done, self.eos, t, k, p, rp, ds, seed)
+
+
+class BatchGraphDecoder:
+    """GraphDecoder for B sequences over a BatchKVCache: the step runs M = B rows through the same ops, with the
+    batched HIP decode attention (csrc/decode_attention.hip) appending each row's K/V and attending over its own
+    slab. ``tok`` / ``pos`` / ``len`` are [B] device tensors, so one captured step serves every token."""
+
+    def __init__(self, model, cache: BatchKVCache):
+        self.model, self.cache = model, cache
+        dev = model.model.embed_tokens.device
+        B = cache.k.shape[1]
+        self.tok = torch.zeros(B, dtype=torch.long, device=dev)
+        self.pos = torch.zeros(B, dtype=torch.long, device=dev)
+        self.len = torch.ones(B, dtype=torch.int32, device=dev)
+        self.graph = None          # model step only (step())
+        self.sampled_graph = None  # model step + sampler (run_sampled())
+        self.logits = None
+
+    @torch.no_grad()
+    def _step(self) -> torch.Tensor:
+        m, cfg = self.model, self.model.config
+        nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        x = ops.embedding(self.tok, m.model.embed_tokens)
+        residual = None
+        cos = sin = None
+        for li, layer in enumerate(m.model.layers):
+            at = layer.self_attn
+            h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
+            qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
+            if at.use_rope:
+                if cos is None:
+                    cos, sin = m.rope_tables(self.pos)
+                ops.rope_(qkv, cos, sin, nq, nkv, D)
+            a = ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv)
+            o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
+            h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
+            x = layer.mlp(h)
+        n = m.model.norm
+        h, _ = ops.add_rms_norm(x, residual, n.weight, cfg.rms_norm_eps)
+        return torch.nn.functional.linear(h, m.lm_head_weight).float()
+
+    def run_sampled(self, sampler: BatchDeviceSampler, n: int, use_graph: bool = True) -> None:
+        """n decode steps of every row entirely on the device (model step + fused sampler in one hipGraph)."""
+        def body():
+            logits = self._step()
+            sampler.sample(logits, self.tok, self.pos, self.len)
+        if not use_graph:
+            for _ in range(n):
+                body()
+            return
+        if self.sampled_graph is None:
+            # warm up on copies of the counters so the real sequence state is untouched
+            live = (self.tok, self.pos, self.len, sampler.state, sampler.presence, sampler.log, sampler.done)
+            saved = [t.clone() for t in live]
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    body()
+            torch.cuda.current_stream().wait_stream(s)
+            for t, v in zip(live, saved):
+                t.copy_(v)
+            self.sampled_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.sampled_graph):
+                body()
+        for _ in range(n):
+            self.sampled_graph.replay()
+
+    def step(self, tokens, use_graph: bool = True, advance=None) -> torch.Tensor:
+        """Decode ``tokens[b]`` at position ``cache.lens[b]`` for every row; returns the logits [B, V] (the graph's
+        static output: clone to keep). Rows with ``advance[b]`` false keep their length (finished sequences)."""
+        lens = self.cache.lens
+        dev = self.tok.device
+        self.tok.copy_(torch.as_tensor(tokens, dtype=torch.long).to(dev))
+        self.pos.copy_(torch.tensor(lens, dtype=torch.long).to(dev))
+        self.len.copy_(torch.tensor([x + 1 for x in lens], dtype=torch.int32).to(dev))
+        for b in range(len(lens)):
+            if advance is None or advance[b]:
+                lens[b] += 1
+        if not use_graph:
+            return self._step()
+        if self.graph is None:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):  # warm up allocator / kernels outside capture
+                    self._step()
+            torch.cuda.current_stream().wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.logits = self._step()
+        self.graph.replay()
+        return self.logits
+
+
+@torch.no_grad()
+def generate_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eos_token_id: Optional[int] = None,
+                   temperature: float = 0.6, top_k: int = 40, top_p: float = 0.95, repetition_penalty: float = 1.1,
+                   do_sample: bool = True, seed: Optional[int] = None, use_graph: Optional[bool] = None,
+                   device_sampling: Optional[bool] = None) -> List[List[int]]:
+    """Element b is what ``generate(model, prompts[b], ..., seed=seed + b)`` returns: every sequence stops at its
+    own EOS (included) or at ``max_new_tokens``. All prompts are prefilled in one packed pass and decoded one
+    token per sequence and step, so the weights are read once per step for the whole batch."""
+    model.eval()
+    B = len(prompts)
+    if B == 0:
+        return []
+    if max_new_tokens <= 0:
+        return [[] for _ in prompts]
+    dev = model.model.embed_tokens.device
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev,
+                         model.model.embed_tokens.dtype)
+    logits = prefill_batch(model, prompts, cache)
+    gpu_path = dev.type == "cuda" and model.config.head_dim == 128 and ops.use_hip(logits)
+    graph = gpu_path if use_graph is None else (use_graph and gpu_path)
+    dec = BatchGraphDecoder(model, cache)
+    if device_sampling is None:
+        device_sampling = DeviceSampler.supported(top_k, do_sample)
+    if gpu_path and device_sampling:
+        return _generate_batch_device(model, dec, prompts, logits, max_new_tokens, eos_token_id, temperature, top_k,
+                                      top_p, repetition_penalty, do_sample, seed, graph)
+    gens = [torch.Generator(device=dev).manual_seed(seed + b) for b in range(B)]
+    hist = [torch.tensor(p, device=dev) for p in prompts]
+    out: List[List[int]] = [[] for _ in prompts]
+    live = [True] * B
+    last = [0] * B
+    for i in range(max_new_tokens):
+        for b in range(B):
+            if not live[b]:
+                continue
+            t = sample_next(logits[b], hist[b], temperature, top_k, top_p, repetition_penalty, do_sample, gens[b])
+            out[b].append(t)
+            last[b] = t
+            if eos_token_id is not None and t == eos_token_id:
+                live[b] = False  # its later steps re-decode the last token in place: wasted, not wrong
+            else:
+                hist[b] = torch.cat([hist[b], torch.tensor([t], device=dev)])
+        if not any(live) or i + 1 == max_new_tokens:
+            break
+        logits = dec.step(last, use_graph=graph, advance=live)
+    return out
+
+
+def _generate_batch_device(model, dec: BatchGraphDecoder, prompts, logits, max_new_tokens, eos_token_id, temperature,
+                           top_k, top_p, repetition_penalty, do_sample, seed, use_graph, check_every: int = 16):
+    """Batched decode loop with sampling on the device. Between bursts of ``check_every`` replays the host reads
+    only the finished flags; it stops when every row is done or has reached its cap, then reads the logs."""
+    dev = model.model.embed_tokens.device
+    sm = BatchDeviceSampler(model.config.vocab_size, dev, prompts, max_new_tokens, seed, eos_token_id, temperature,
+                            top_k, top_p, repetition_penalty, do_sample)
+    sm.state[:, 2] = torch.tensor([len(p) - 1 for p in prompts], device=dev)  # first sampled token: position len(p)
+    sm.sample(logits, dec.tok, dec.pos, dec.len)  # token 1 of every row from the prefill logits
+    steps = 1
+    while steps < max_new_tokens and not bool(sm.done.all()):
+        n = min(check_every, max_new_tokens - steps)
+        dec.run_sampled(sm, n, use_graph=use_graph)
+        steps += n
+    counts = sm.state[:, 0].tolist()  # tokens drawn per row: a finished row stops counting
+    log = sm.log.tolist()
+    return [log[b][:counts[b]] for b in range(len(prompts))]

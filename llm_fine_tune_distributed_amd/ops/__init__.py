@@ -6,6 +6,7 @@ from .fused import (
     add_rms_norm,
     bump_param_epoch,
     decode_attention,
+    decode_attention_batched,
     dgrad_mm,
     dropout_add,
     embedding,
@@ -35,7 +36,7 @@ from .fused import (
 from .optim_kernels import adamw_flat_, grad_norm_flat, sumsq_list
 
 __all__ = [
-    "reference", "load_extension", "use_hip", "hip_disabled", "IGNORE_INDEX", "add_rms_norm", "bump_param_epoch", "decode_attention", "dropout_add",
+    "reference", "load_extension", "use_hip", "hip_disabled", "IGNORE_INDEX", "add_rms_norm", "bump_param_epoch", "decode_attention", "decode_attention_batched", "dropout_add",
     "attn_out_linear", "qkv_in_linear", "wgrad_carry_scope", "embedding", "flash_attention", "linear", "linear_rope", "linear_swiglu", "lora_inplace_ok", "lora_linear", "lora_qkv_rope_attention", "lora_swiglu_mlp", "lm_head_cross_entropy", "qkv_rope_attention", "register_param_sync", "rms_norm", "rope_", "set_cu_budget", "cu_budget", "swiglu",
     "swiglu_linear", "swiglu_mlp", "dgrad_mm", "fuse_swiglu_down", "adamw_flat_", "grad_norm_flat", "sumsq_list",
 ]

@@ -1783,3 +1783,28 @@ def decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, scale=None):
     qg = q.float().view(n_kv, n_q // n_kv, D)
     att = torch.einsum("grd,sgd->grs", qg, kcache[:L].float()) * scale
     return torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[:L].float()).reshape(-1).to(q.dtype)
+
+
+def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None):
+    """One decode step of B sequences. ``qkv`` [B, (n_q + 2 n_kv) * D] is the step's post-RoPE projection,
+    ``kcache`` / ``vcache`` [B, S_max, n_kv, D] one slab per sequence, ``lens`` [B] int32 the live length of each
+    sequence INCLUDING the token being decoded. Row b's K/V are appended at ``cache[b, lens[b] - 1]`` (a length
+    outside (0, S_max] skips the row), then row b attends over ``cache[b, :lens[b]]``. Returns [B, n_q * D].
+    The HIP kernel is built for head_dim 128; other head dims decode in torch, as they do in forward_cached."""
+    B = qkv.shape[0]
+    D = qkv.shape[1] // (n_q + 2 * n_kv)
+    if _ext.use_hip(qkv) and D == 128:
+        scale = scale if scale is not None else 1.0 / math.sqrt(D)
+        return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale))
+    out = torch.zeros(B, n_q * D, dtype=qkv.dtype, device=qkv.device)
+    smax = kcache.shape[1]
+    for b, L in enumerate(lens.tolist()):
+        if not 0 < L <= smax:
+            continue
+        kcache[b, L - 1] = qkv[b, n_q * D:(n_q + n_kv) * D].view(n_kv, D)
+        vcache[b, L - 1] = qkv[b, (n_q + n_kv) * D:].view(n_kv, D)
+        qg = qkv[b, :n_q * D].float().view(n_kv, n_q // n_kv, D)
+        att = torch.einsum("grd,sgd->grs", qg, kcache[b, :L].float())
+        att = att / math.sqrt(D) if scale is None else att * scale  # the default divides, as forward_cached does
+        out[b] = torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[b, :L].float()).reshape(-1).to(qkv.dtype)
+    return out
