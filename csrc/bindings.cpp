@@ -62,6 +62,10 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("cu_hog(Tensor(a!) sink, int blocks, float usec) -> ()");
   m.def("swiglu_bwd(Tensor dy, Tensor gate_up) -> Tensor");
   m.def("rope_(Tensor(a!) qkv, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim, bool inverse) -> ()");
+  // per-head QK RMSNorm + RoPE, in place on the q|k columns of the packed qkv (csrc/qk_norm.hip); fwd returns the raw
+  // q|k copy for the backward (empty with save_raw=False), bwd returns (dq_weight, dk_weight) in fp32
+  m.def("qk_norm_rope_fwd(Tensor(a!) qkv, Tensor q_weight, Tensor k_weight, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim, float eps, bool save_raw=True) -> Tensor");
+  m.def("qk_norm_rope_bwd(Tensor(a!) dqkv, Tensor qk_raw, Tensor q_weight, Tensor k_weight, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim, float eps) -> (Tensor, Tensor)");
   m.def("embedding_fwd(Tensor ids, Tensor weight) -> Tensor");
   m.def("dropout_add(Tensor? a, Tensor b, float p, int seed) -> Tensor");
   m.def("lora_widen(Tensor x, int R, float p, int seed) -> (Tensor, Tensor)");

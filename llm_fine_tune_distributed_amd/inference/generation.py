@@ -33,6 +33,18 @@ class KVCache:
         self.len = 0
 
 
+def _rotate_qk_(at, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> None:
+    """What a RoPE layer does to the q|k columns of the packed qkv between the projection and attention, in place:
+    the rotation, behind the per-head RMSNorm for a qk-norm model (Qwen3; one kernel, and under no_grad it keeps no
+    copy for a backward). Shape-static for M = 1..B rows, so the graph decoders capture it."""
+    c = at.cfg
+    nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+    if at.qk_norm:
+        ops.qk_norm_rope_(qkv, at.q_norm.weight, at.k_norm.weight, cos, sin, nq, nkv, D, at.q_norm.eps)
+    else:
+        ops.rope_(qkv, cos, sin, nq, nkv, D)
+
+
 @torch.no_grad()
 def _layer(model, li, x, residual, cache: KVCache, pos: torch.Tensor, prefill: bool):
     cfg = model.config
@@ -43,7 +55,7 @@ def _layer(model, li, x, residual, cache: KVCache, pos: torch.Tensor, prefill: b
     qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
     if at.use_rope:
         cos, sin = model.rope_tables(pos)
-        ops.rope_(qkv, cos, sin, nq, nkv, D)
+        _rotate_qk_(at, qkv, cos, sin)
     M = qkv.shape[0]
     k = qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D)
     v = qkv[:, (nq + nkv) * D:].view(M, nkv, D)
@@ -165,7 +177,7 @@ class GraphDecoder:
             if at.use_rope:
                 if cos is None:
                     cos, sin = m.rope_tables(self.pos)
-                ops.rope_(qkv, cos, sin, nq, nkv, D)
+                _rotate_qk_(at, qkv, cos, sin)
             self.cache.k[li].index_copy_(0, self.pos, qkv[:, nq * D:(nq + nkv) * D].view(1, nkv, D))
             self.cache.v[li].index_copy_(0, self.pos, qkv[:, (nq + nkv) * D:].view(1, nkv, D))
             a = ops.decode_attention(qkv[0, :nq * D].contiguous(), self.cache.k[li], self.cache.v[li], self.len,
@@ -327,7 +339,7 @@ def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch
         if at.use_rope:
             if cos is None:
                 cos, sin = model.rope_tables(pos)
-            ops.rope_(qkv, cos, sin, nq, nkv, D)
+            _rotate_qk_(at, qkv, cos, sin)
         cache.k[li][seq, pos] = qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D)
         cache.v[li][seq, pos] = qkv[:, (nq + nkv) * D:].view(M, nkv, D)
         a = ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D)
@@ -399,7 +411,7 @@ class BatchGraphDecoder:
             if at.use_rope:
                 if cos is None:
                     cos, sin = m.rope_tables(self.pos)
-                ops.rope_(qkv, cos, sin, nq, nkv, D)
+                _rotate_qk_(at, qkv, cos, sin)
             a = ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv)
             o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
             h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)

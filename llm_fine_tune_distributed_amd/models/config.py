@@ -39,9 +39,14 @@ class ModelConfig:
     eos_token_id: Optional[int] = 128001
     pad_token_id: Optional[int] = 128004
     torch_dtype: str = "bfloat16"
+    # RMSNorm over every query and key head after the projection, before RoPE (Qwen3: self_attn.q_norm / k_norm).
+    # None: decided by the model type.
+    qk_norm: Optional[bool] = None
     extra: Dict[str, Any] = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.qk_norm is None:
+            self.qk_norm = self.model_type == "qwen3"
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
         if self.num_key_value_heads is None:
@@ -74,6 +79,8 @@ class ModelConfig:
     def num_parameters(self) -> int:
         h, i, v = self.hidden_size, self.intermediate_size, self.vocab_size
         per_layer = h * self.qkv_size + self.q_size * h + 3 * h * i + 2 * h
+        if self.qk_norm:
+            per_layer += 2 * self.head_dim
         emb = v * h
         head = 0 if self.tie_word_embeddings else v * h
         return self.num_hidden_layers * per_layer + emb + head + h
@@ -93,7 +100,8 @@ class ModelConfig:
 
     # ------------------------------------------------------------------ (de)serialisation
     def to_hf_dict(self) -> Dict[str, Any]:
-        arch = {"smollm3": "SmolLM3ForCausalLM", "llama": "LlamaForCausalLM"}.get(self.model_type, "LlamaForCausalLM")
+        arch = {"smollm3": "SmolLM3ForCausalLM", "llama": "LlamaForCausalLM",
+                "qwen3": "Qwen3ForCausalLM"}.get(self.model_type, "LlamaForCausalLM")
         d = {
             "architectures": [arch],
             "model_type": self.model_type,
@@ -121,6 +129,9 @@ class ModelConfig:
         if self.model_type == "smollm3":
             d["no_rope_layers"] = list(self.no_rope_layers[: self.num_hidden_layers])
             d["no_rope_layer_interval"] = self.no_rope_layer_interval
+        if self.model_type == "qwen3":
+            del d["mlp_bias"]  # not a Qwen3Config key
+            d["use_sliding_window"] = False
         d.update(self.extra)
         return d
 
@@ -138,8 +149,17 @@ class ModelConfig:
         if isinstance(kw.get("eos_token_id"), list):
             kw["eos_token_id"] = kw["eos_token_id"][0]
         kw.setdefault("model_type", d.get("model_type", "llama"))
-        if kw["model_type"] not in ("smollm3", "llama"):
+        if kw["model_type"] not in ("smollm3", "llama", "qwen3"):
             kw["model_type"] = "llama"
+        if kw["model_type"] == "qwen3":
+            # what a Qwen3 config may ask for and this model does not implement: fail here, not in the weights loader
+            if d.get("attention_bias"):
+                raise NotImplementedError("qwen3: attention_bias=true is not supported (the projections have no bias)")
+            if d.get("use_sliding_window"):
+                raise NotImplementedError("qwen3: use_sliding_window=true is not supported (full attention only)")
+            bad = sorted({t for t in (d.get("layer_types") or []) if t != "full_attention"})
+            if bad:
+                raise NotImplementedError(f"qwen3: layer_types {bad} are not supported (full_attention only)")
         return cls(**kw)
 
     @classmethod
@@ -169,6 +189,26 @@ def llama3_8b() -> ModelConfig:
     )
 
 
+# The two Qwen3 shapes below are written from memory of the published config.json files (no copy of them was at hand):
+# a real checkpoint directory's own config.json always wins (get_config on the directory).
+def _qwen3(**kw) -> ModelConfig:
+    base = dict(model_type="qwen3", vocab_size=151936, num_hidden_layers=36, num_attention_heads=32,
+                num_key_value_heads=8, head_dim=128, rope_theta=1_000_000.0, rms_norm_eps=1e-6,
+                max_position_embeddings=40960, bos_token_id=151643, eos_token_id=151645, pad_token_id=None)
+    base.update(kw)
+    return ModelConfig(**base)
+
+
+def qwen3_4b() -> ModelConfig:
+    """Qwen/Qwen3-4B shape (tied embeddings; q width 32 x 128 = 4096 > hidden 2560)."""
+    return _qwen3(hidden_size=2560, intermediate_size=9728, tie_word_embeddings=True)
+
+
+def qwen3_8b() -> ModelConfig:
+    """Qwen/Qwen3-8B shape (untied lm_head)."""
+    return _qwen3(hidden_size=4096, intermediate_size=12288, tie_word_embeddings=False)
+
+
 def tiny(model_type: str = "smollm3", **kw) -> ModelConfig:
     """Small config with the same structure (GQA, NoPE interval, tied head) for tests."""
     base = dict(
@@ -191,6 +231,13 @@ PRESETS = {
     # tiny depth/width with the real head_dim (128) the HIP attention kernels are built for (GPU tests)
     "tiny-gpu": lambda: tiny(hidden_size=256, num_attention_heads=2, num_key_value_heads=1, head_dim=128,
                              intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
+    "qwen3-4b": qwen3_4b,
+    "Qwen/Qwen3-4B": qwen3_4b,
+    "qwen3-8b": qwen3_8b,
+    "Qwen/Qwen3-8B": qwen3_8b,
+    "tiny-qwen3": lambda: tiny("qwen3"),
+    "tiny-gpu-qwen3": lambda: tiny("qwen3", hidden_size=256, num_attention_heads=2, num_key_value_heads=1,
+                                   head_dim=128, intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
 }
 
 

@@ -1,4 +1,4 @@
-"""Decoder-only causal LM (SmolLM3 / Llama family) built on the fused ops.
+"""Decoder-only causal LM (SmolLM3 / Llama / Qwen3 families) built on the fused ops.
 
 Replaces ``AutoModelForCausalLM.from_pretrained(...)`` of the reference
 (``training.py:97-105``) and the transformers modules it runs
@@ -53,12 +53,18 @@ class Attention(nn.Module):
         self.use_rope = cfg.uses_rope(layer_idx)
         self.qkv_proj = nn.Parameter(torch.empty(cfg.qkv_size, cfg.hidden_size))
         self.o_proj = nn.Parameter(torch.empty(cfg.hidden_size, cfg.q_size))
+        self.qk_norm = bool(cfg.qk_norm)
+        if self.qk_norm:  # Qwen3: RMSNorm over each query / key head (one weight [head_dim] per layer), before RoPE
+            self.q_norm = RMSNorm(cfg.head_dim, cfg.rms_norm_eps)
+            self.k_norm = RMSNorm(cfg.head_dim, cfg.rms_norm_eps)
         self.lora = None  # set by apply_lora
         self.cp_group = None  # context-parallel process group (CausalLM.enable_context_parallel)
         self.cp_layout = "zigzag"
 
     def forward(self, h, rope_cs, cu_seqlens, max_seqlen):
         c = self.cfg
+        if self.qk_norm:
+            return self._forward_qk_norm(h, rope_cs, cu_seqlens, max_seqlen)
         if self.lora is None and self.use_rope and self.cp_group is None:
             # projection + RoPE (GEMM epilogue) + attention as one autograd node: the backward applies the inverse
             # rotation inside the attention kernels' dq / dK epilogues
@@ -95,6 +101,30 @@ class Attention(nn.Module):
                                     c.head_dim, delta_box=box)
             if box is not None:
                 return ops.attn_out_linear(a, self.o_proj, box)
+        return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
+
+    def _forward_qk_norm(self, h, rope_cs, cu_seqlens, max_seqlen):
+        """A qk-norm layer (Qwen3): projection, then the per-head norm + RoPE in place on the GEMM output, then
+        attention. The norm sits between the GEMM and the rotation, so the fused qkv + RoPE epilogue does not apply:
+        this is the NoPE layer's composition (o_proj + qkv weight gradients as one launch, carried into the previous
+        MLP's; the attention delta from the o_proj dgrad epilogue) with the new node in the middle. The projection
+        node saves its input, not its output, so the in-place node modifies nothing another node has saved."""
+        c = self.cfg
+        nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        assert self.use_rope, "qk-norm layers rotate on every layer"
+        plain = self.lora is None and self.cp_group is None
+        pair = {} if plain else None
+        qkv = (ops.qkv_in_linear(h, self.qkv_proj, pair) if self.lora is None
+               else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
+        qkv = ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, rope_cs[0], rope_cs[1], nq, nkv, D,
+                                self.q_norm.eps)
+        if self.cp_group is not None:
+            from ..parallel.context_parallel import ring_attention
+            a = ring_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, self.cp_group, layout=self.cp_layout)
+        else:
+            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, delta_box=pair)
+            if pair is not None:
+                return ops.attn_out_linear(a, self.o_proj, pair)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
 
 
@@ -155,7 +185,7 @@ class Model(nn.Module):
 
 
 class CausalLM(nn.Module):
-    """SmolLM3ForCausalLM / LlamaForCausalLM equivalent."""
+    """SmolLM3ForCausalLM / LlamaForCausalLM / Qwen3ForCausalLM equivalent."""
 
     def __init__(self, cfg: ModelConfig):
         super().__init__()
@@ -329,6 +359,9 @@ class CausalLM(nn.Module):
             sd[p + "self_attn.k_proj.weight"] = k
             sd[p + "self_attn.v_proj.weight"] = v
             sd[p + "self_attn.o_proj.weight"] = l.self_attn.o_proj.detach()
+            if l.self_attn.qk_norm:
+                sd[p + "self_attn.q_norm.weight"] = l.self_attn.q_norm.weight.detach()
+                sd[p + "self_attn.k_norm.weight"] = l.self_attn.k_norm.weight.detach()
             g, u = l.mlp.gate_up_proj.detach().split([cfg.intermediate_size] * 2, 0)
             sd[p + "mlp.gate_proj.weight"] = g
             sd[p + "mlp.up_proj.weight"] = u
@@ -356,6 +389,9 @@ class CausalLM(nn.Module):
                                                   take(p + "self_attn.k_proj.weight"),
                                                   take(p + "self_attn.v_proj.weight")], 0))
             l.self_attn.o_proj.copy_(take(p + "self_attn.o_proj.weight"))
+            if l.self_attn.qk_norm:
+                l.self_attn.q_norm.weight.copy_(take(p + "self_attn.q_norm.weight"))
+                l.self_attn.k_norm.weight.copy_(take(p + "self_attn.k_norm.weight"))
             l.mlp.gate_up_proj.copy_(torch.cat([take(p + "mlp.gate_proj.weight"), take(p + "mlp.up_proj.weight")], 0))
             l.mlp.down_proj.copy_(take(p + "mlp.down_proj.weight"))
             l.input_layernorm.weight.copy_(take(p + "input_layernorm.weight"))

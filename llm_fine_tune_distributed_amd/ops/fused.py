@@ -1,4 +1,4 @@
-"""Autograd Functions for the SmolLM3/Llama hot path.
+"""Autograd Functions for the SmolLM3/Llama/Qwen3 hot path.
 
 Every Function is device-agnostic: on GPU tensors it calls the CDNA4 HIP kernels in
 ``torch.ops.sftamd`` (csrc/*.hip); on CPU tensors it runs ``ops.reference``. The same
@@ -1063,6 +1063,64 @@ def _rope_inplace(qkv, cos, sin, n_q, n_kv, hd, inverse):
 
 def rope_(qkv, cos, sin, n_q, n_kv, head_dim):
     return RoPEFn.apply(qkv, cos, sin, n_q, n_kv, head_dim)
+
+
+# ----------------------------------------------------------------------------- QK RMSNorm + RoPE (in place, Qwen3)
+def _qk_norm_hip(qkv: torch.Tensor, head_dim: int) -> bool:
+    """The HIP kernels (csrc/qk_norm.hip) are built for head_dim 128 (every Qwen3 size); other head sizes take the
+    reference. What the op cannot take at head_dim 128 (dtype, layout) fails its checks: no silent reference run."""
+    return _ext.use_hip(qkv) and head_dim == 128
+
+
+def _qk_norm_rope_fwd_inplace(qkv, qw, kw, cos, sin, n_q, n_kv, hd, eps, save_raw: bool):
+    """qkv's q|k columns <- rope(rmsnorm_per_head(q|k)); returns the raw q|k copy (None unless save_raw)."""
+    if _qk_norm_hip(qkv, hd):
+        raw = _ext.ops().qk_norm_rope_fwd(qkv, qw, kw, cos, sin, n_q, n_kv, hd, float(eps), save_raw)
+        return raw if save_raw else None
+    w = (n_q + n_kv) * hd
+    raw = qkv[:, :w].clone() if save_raw else None
+    qkv[:, :w].copy_(ref.qk_norm_rope(qkv, qw, kw, cos, sin, n_q, n_kv, hd, eps)[:, :w])
+    return raw
+
+
+class QKNormRopeFn(Function):
+    """In place on the packed qkv [M, (n_q + 2 n_kv) * D]: every q / k head row <- rope(w * rmsnorm(row)), w = the
+    layer's q_norm / k_norm weight [D] (ops.reference.qk_norm_rope). The raw q|k columns are saved for the backward
+    (rstd is recomputed from them); the backward works in place on the incoming gradient and returns it."""
+
+    @staticmethod
+    def forward(ctx, qkv, qw, kw, cos, sin, n_q, n_kv, head_dim, eps):
+        raw = _qk_norm_rope_fwd_inplace(qkv, qw, kw, cos, sin, n_q, n_kv, head_dim, eps, save_raw=True)
+        ctx.save_for_backward(raw, cos, sin)
+        ctx.qw, ctx.kw = qw, kw
+        ctx.dims = (n_q, n_kv, head_dim, eps)
+        ctx.mark_dirty(qkv)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        raw, cos, sin = ctx.saved_tensors
+        qw, kw = ctx.qw, ctx.kw
+        n_q, n_kv, hd, eps = ctx.dims
+        dqkv = dqkv.contiguous()
+        if _qk_norm_hip(dqkv, hd):
+            dqw, dkw = _ext.ops().qk_norm_rope_bwd(dqkv, raw, qw, kw, cos, sin, n_q, n_kv, hd, float(eps))
+        else:
+            dx, dqw, dkw = ref.qk_norm_rope_bwd(dqkv, raw, qw, kw, cos, sin, n_q, n_kv, hd, eps)
+            dqkv[:, : (n_q + n_kv) * hd].copy_(dx)
+        gq = _accumulate_small_grad(qw, dqw) if ctx.needs_input_grad[1] else None
+        gk = _accumulate_small_grad(kw, dkw) if ctx.needs_input_grad[2] else None
+        return dqkv, gq, gk, None, None, None, None, None, None
+
+
+def qk_norm_rope_(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps):
+    """Per-head QK RMSNorm + RoPE in place on the packed qkv (returns qkv). With nothing to differentiate
+    (torch.no_grad(): generation) the raw q|k copy for the backward is not written and no autograd node is made, so
+    the call is one kernel and can be captured into a graph."""
+    if not (torch.is_grad_enabled() and (qkv.requires_grad or q_weight.requires_grad or k_weight.requires_grad)):
+        _qk_norm_rope_fwd_inplace(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps, save_raw=False)
+        return qkv
+    return QKNormRopeFn.apply(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps)
 
 
 # ----------------------------------------------------------------------------- attention

@@ -56,7 +56,7 @@ def rope_inv_freq(head_dim: int, theta: float, scaling: Optional[dict], device=N
 def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     """x [M, H, D]; cos/sin [M, D/2]. rotate_half convention (HF Llama/SmolLM3)."""
     d2 = x.shape[-1] // 2
-    xf = x.float()
+    xf = x if x.dtype == torch.float64 else x.float()  # (fp64 stays fp64: gradient checks)
     x1, x2 = xf[..., :d2], xf[..., d2:]
     c, s = cos[:, None, :], sin[:, None, :]
     if inverse:
@@ -64,6 +64,43 @@ def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, inverse: b
     o1 = x1 * c - x2 * s
     o2 = x2 * c + x1 * s
     return torch.cat([o1, o2], dim=-1).to(x.dtype)
+
+
+def _qk_weights(qw: torch.Tensor, kw: torch.Tensor, n_q: int, n_kv: int, dtype) -> torch.Tensor:
+    """[n_q + n_kv, D]: the q_norm weight for the query heads, the k_norm weight for the key heads."""
+    return torch.cat([qw.to(dtype).expand(n_q, -1), kw.to(dtype).expand(n_kv, -1)], 0)
+
+
+def qk_norm_rope(qkv: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                 n_q: int, n_kv: int, head_dim: int, eps: float) -> torch.Tensor:
+    """Per-head QK RMSNorm + RoPE on the packed qkv [M, (n_q + 2 n_kv) * D] (Qwen3): every q and k head row becomes
+    rope(w * x * rsqrt(mean(x^2) + eps)) with w = qw [D] for the query heads and kw [D] for the key heads; the V
+    columns pass through. Math in fp32 (fp64 for fp64 inputs), one rounding to the input dtype. Out of place and
+    differentiable by autograd in qkv, qw and kw."""
+    M, nh, D = qkv.shape[0], n_q + n_kv, head_dim
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    x = qkv[:, : nh * D].to(ct).view(M, nh, D)
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    n = x * rstd * _qk_weights(qw, kw, n_q, n_kv, ct)[None]
+    y = apply_rope(n, cos.to(ct), sin.to(ct))
+    return torch.cat([y.reshape(M, nh * D).to(qkv.dtype), qkv[:, nh * D:]], dim=-1)
+
+
+def qk_norm_rope_bwd(dqkv: torch.Tensor, qk_raw: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor, cos: torch.Tensor,
+                     sin: torch.Tensor, n_q: int, n_kv: int, head_dim: int, eps: float):
+    """Backward of qk_norm_rope in closed form (the math of csrc/qk_norm.hip): dqkv is the gradient w.r.t. the output,
+    qk_raw [M, (n_q + n_kv) * D] the un-normalised q|k input. Returns (dx [M, (n_q + n_kv) * D] in dqkv's dtype,
+    dq_weight [D], dk_weight [D]); the weight gradients are fp32 (fp64 for fp64 inputs)."""
+    M, nh, D = dqkv.shape[0], n_q + n_kv, head_dim
+    ct = torch.float64 if dqkv.dtype == torch.float64 else torch.float32
+    x = qk_raw.to(ct).view(M, nh, D)
+    g = apply_rope(dqkv[:, : nh * D].to(ct).view(M, nh, D), cos.to(ct), sin.to(ct), inverse=True)
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    xh = x * rstd
+    gw = g * _qk_weights(qw, kw, n_q, n_kv, ct)[None]
+    dx = rstd * (gw - xh * (gw * xh).mean(-1, keepdim=True))
+    gx = g * xh
+    return (dx.reshape(M, nh * D).to(dqkv.dtype), gx[:, :n_q].sum((0, 1)), gx[:, n_q:].sum((0, 1)))
 
 
 def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens: torch.Tensor,
