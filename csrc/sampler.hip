@@ -29,12 +29,33 @@ constexpr int TILE = NT * IPT;          // 2048 logits per block
 constexpr int IPT2 = 16;                // keys per thread, final pass (4096 candidates)
 constexpr int KMAX = 64;                // top-k supported on the device path
 
+// IPT consecutive logits i0 .. i0 + IPT - 1 of a row as floats (elements at or past V are left unset): 16-byte vector
+// loads when the run is whole and aligned (a row of a [B, V] batch with odd V is not), element loads otherwise.
 template <typename T>
-__device__ __forceinline__ float to_f(T v);
+__device__ __forceinline__ void load_run(const T* __restrict__ logits, int i0, int V, float* raw);
 template <>
-__device__ __forceinline__ float to_f<float>(float v) { return v; }
+__device__ __forceinline__ void load_run<float>(const float* __restrict__ logits, int i0, int V, float* raw) {
+  const float* p = logits + i0;
+  if (i0 + IPT <= V && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    *(float4*)&raw[0] = *(const float4*)p;
+    *(float4*)&raw[4] = *(const float4*)(p + 4);
+  } else {
+#pragma unroll
+    for (int j = 0; j < IPT; ++j)
+      if (i0 + j < V) raw[j] = p[j];
+  }
+}
 template <>
-__device__ __forceinline__ float to_f<u16>(u16 v) { return bf2f(v); }
+__device__ __forceinline__ void load_run<u16>(const u16* __restrict__ logits, int i0, int V, float* raw) {
+  const u16* p = logits + i0;
+  if (i0 + IPT <= V && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    unpack8(*(const uint4*)p, raw);
+  } else {
+#pragma unroll
+    for (int j = 0; j < IPT; ++j)
+      if (i0 + j < V) raw[j] = bf2f(p[j]);
+  }
+}
 
 // One 2048-logit tile of one row (shared by the single-row and the batched kernel): logits / presence / cand_* point
 // at the row, ``tile`` is the tile's index within it.
@@ -47,14 +68,21 @@ __device__ __forceinline__ void partial_body(const T* __restrict__ logits, int V
   __shared__ typename Sort::storage_type storage;
   float key[IPT];
   int idx[IPT];
-  const int base = tile * TILE;
+  // Blocked loads: thread t holds logits i0 .. i0 + IPT - 1 in index order. The radix sort is stable and its input
+  // order is (thread, j), so equal keys keep their index order and a tie at the top resolves to the LOWEST index, as
+  // argmax does on the host path (striped loads resolved a tie between indices 1 and 256 of a tile to 256).
+  const int i0 = tile * TILE + threadIdx.x * IPT;
+  float raw[IPT];
+  load_run<T>(logits, i0, V, raw);
+  // i0 is a multiple of IPT = 8: the 8 presence bits of the run sit in one word
+  const unsigned pres = (penalty != 1.f && i0 < V) ? (presence[i0 >> 5] >> (i0 & 31)) & 0xffu : 0u;
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
-    const int i = base + j * NT + threadIdx.x;  // striped loads: coalesced
+    const int i = i0 + j;
     float x = -INFINITY;
     if (i < V) {
-      x = to_f<T>(logits[i]);
-      if (penalty != 1.f && ((presence[i >> 5] >> (i & 31)) & 1u)) x = x < 0.f ? x * penalty : x / penalty;
+      x = raw[j];
+      if ((pres >> j) & 1u) x = x < 0.f ? x * penalty : x / penalty;
       x *= inv_temp;
     }
     key[j] = x;
@@ -111,7 +139,7 @@ __device__ __forceinline__ void final_body(const float* __restrict__ cand_v, con
   int idx[IPT2];
 #pragma unroll
   for (int j = 0; j < IPT2; ++j) {
-    const int c = j * NT + threadIdx.x;
+    const int c = threadIdx.x * IPT2 + j;  // blocked: candidates are (tile, rank)-ordered, so ties keep index order
     key[j] = c < ncand ? cand_v[c] : -INFINITY;
     idx[j] = c < ncand ? cand_i[c] : 0x7fffffff;
   }
@@ -213,7 +241,7 @@ void sample_token(const at::Tensor& logits, at::Tensor presence, at::Tensor stat
             "sample_token: presence int32 bitmask");
   SFT_CHECK(state.scalar_type() == at::kLong && state.numel() >= 4, "sample_token: state int64[4]");
   const int K = do_sample ? (int)top_k : 1;
-  SFT_CHECK(K >= 1 && K <= samp::KMAX, "sample_token: top_k must be in [1, 64] on the device path");
+  SFT_CHECK(K >= 1 && K <= samp::KMAX && K <= V, "sample_token: top_k must be in [1, min(64, V)] on the device path");
   const int nblk = (V + samp::TILE - 1) / samp::TILE;
   SFT_CHECK(nblk * K <= samp::NT * samp::IPT2, "sample_token: vocabulary too large for one merge block");
   SFT_CHECK(!pos_out.has_value() || (len_out.has_value() && pos_out->scalar_type() == at::kLong &&
