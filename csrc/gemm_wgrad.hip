@@ -422,44 +422,42 @@ void g4_wgrad_pair(const at::Tensor& dy0, const at::Tensor& x0, at::Tensor& out0
                    const at::Tensor& dy1, const at::Tensor& x1, at::Tensor& out1, bool acc1, float* nrm1, long cap1,
                    int split_all);
 
+// One problem of a multi-problem launch, checked: bf16 operands, dy and out contiguous, x with contiguous rows (a
+// padded row pitch is fine), out [N, K] for dy [T, N] and x [T, K]. norm: fp32 gradient-norm partial slots; absent,
+// undefined or empty = none for this problem.
+static WgradJob checked_job(const char* op, const at::Tensor& out, const at::Tensor& dy, const at::Tensor& x, bool acc,
+                            const c10::optional<at::Tensor>& norm) {
+  SFT_CHECK_CUDA(dy);
+  SFT_CHECK_BF16(out);
+  SFT_CHECK_BF16(dy);
+  SFT_CHECK_BF16(x);
+  SFT_CHECK_CONTIG(dy);
+  SFT_CHECK_CONTIG(out);
+  SFT_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= x.size(1), op,
+            ": x rows contiguous");
+  SFT_CHECK(out.size(0) == dy.size(1) && out.size(1) == x.size(1), op, ": shape mismatch");
+  WgradJob job{dy, x, out, acc, nullptr, 0};
+  if (norm.has_value() && norm->defined() && norm->numel() > 0) {
+    SFT_CHECK(norm->scalar_type() == at::kFloat && norm->is_contiguous() && norm->is_cuda(), op, ": fp32 norm slots");
+    job.nrm = norm->data_ptr<float>();
+    job.cap = norm->numel();
+  }
+  return job;
+}
+
 // Two weight gradients over the same tokens in ONE 4-wave launch (e.g. the MLP's down and gate_up: 344 + 688 tiles =
-// 4.03 rounds instead of 1.34 + 2.69 with a partial last round each; csrc/gemm_4w.hip g4_wgrad_pair).
+// 4.03 rounds instead of 1.34 + 2.69 with a partial last round each; csrc/gemm_4w.hip g4_wgrad_pair, which checks that
+// the partial round falls in the second problem).
 void wgrad_gemm_pair(at::Tensor out0, at::Tensor dy0, at::Tensor x0, bool acc0, const c10::optional<at::Tensor>& norm0,
                      at::Tensor out1, at::Tensor dy1, at::Tensor x1, bool acc1,
                      const c10::optional<at::Tensor>& norm1, int64_t split_all) {
-  SFT_CHECK_CUDA(dy0);
-  SFT_CHECK_BF16(out0);
-  SFT_CHECK_BF16(dy0);
-  SFT_CHECK_BF16(x0);
-  SFT_CHECK_BF16(out1);
-  SFT_CHECK_BF16(dy1);
-  SFT_CHECK_BF16(x1);
-  SFT_CHECK_CONTIG(dy0);
-  SFT_CHECK_CONTIG(dy1);
-  SFT_CHECK_CONTIG(out0);
-  SFT_CHECK_CONTIG(out1);
-  SFT_CHECK(x0.dim() == 2 && x0.stride(1) == 1 && x0.stride(0) % 8 == 0 && x0.stride(0) >= x0.size(1) &&
-                x1.dim() == 2 && x1.stride(1) == 1 && x1.stride(0) % 8 == 0 && x1.stride(0) >= x1.size(1),
-            "wgrad_gemm_pair: x rows contiguous");
-  SFT_CHECK(out0.size(0) == dy0.size(1) && out0.size(1) == x0.size(1) && out1.size(0) == dy1.size(1) &&
-                out1.size(1) == x1.size(1), "wgrad_gemm_pair: shape mismatch");
-  auto slots = [](const c10::optional<at::Tensor>& n, float*& p, long& cap) {
-    p = nullptr;
-    cap = 0;
-    if (n.has_value() && n->defined()) {
-      SFT_CHECK(n->scalar_type() == at::kFloat && n->is_contiguous() && n->is_cuda(), "wgrad_gemm_pair: fp32 norm slots");
-      p = n->data_ptr<float>();
-      cap = n->numel();
-    }
-  };
-  float *n0, *n1;
-  long c0, c1;
-  slots(norm0, n0, c0);
-  slots(norm1, n1, c1);
+  WgradJob j0 = checked_job("wgrad_gemm_pair", out0, dy0, x0, acc0, norm0);
+  WgradJob j1 = checked_job("wgrad_gemm_pair", out1, dy1, x1, acc1, norm1);
   SFT_TRACE("wgrad.pair");
-  if (n0 != nullptr || n1 != nullptr) SFT_TRACE("wgrad.norm_slots");
+  if (j0.nrm != nullptr || j1.nrm != nullptr) SFT_TRACE("wgrad.norm_slots");
   SFT_CHECK(split_all >= 0 && split_all <= 8, "wgrad_gemm_pair: split_all 0..8");
-  g4_wgrad_pair(dy0, x0, out0, acc0, n0, c0, dy1, x1, out1, acc1, n1, c1, (int)split_all);
+  g4_wgrad_pair(j0.dy, j0.x, j0.out, j0.acc, j0.nrm, j0.cap, j1.dy, j1.x, j1.out, j1.acc, j1.nrm, j1.cap,
+                (int)split_all);
 }
 
 // Up to four weight gradients over the same tokens in ONE 4-wave launch (csrc/gemm_4w.hip g4_wgrad_multi), e.g. a
@@ -475,25 +473,8 @@ void wgrad_gemm_multi(at::TensorList outs, at::TensorList dys, at::TensorList xs
   std::vector<WgradJob> jobs;
   bool any_norm = false;
   for (size_t i = 0; i < n; ++i) {
-    const at::Tensor &out = outs[i], &dy = dys[i], &x = xs[i], &nr = norms[i];
-    SFT_CHECK_CUDA(dy);
-    SFT_CHECK_BF16(out);
-    SFT_CHECK_BF16(dy);
-    SFT_CHECK_BF16(x);
-    SFT_CHECK_CONTIG(dy);
-    SFT_CHECK_CONTIG(out);
-    SFT_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= x.size(1),
-              "wgrad_gemm_multi: x rows contiguous");
-    SFT_CHECK(out.size(0) == dy.size(1) && out.size(1) == x.size(1), "wgrad_gemm_multi: shape mismatch");
-    float* np = nullptr;
-    long cap = 0;
-    if (nr.defined() && nr.numel() > 0) {
-      SFT_CHECK(nr.scalar_type() == at::kFloat && nr.is_contiguous() && nr.is_cuda(), "wgrad_gemm_multi: fp32 norm slots");
-      np = nr.data_ptr<float>();
-      cap = nr.numel();
-      any_norm = true;
-    }
-    jobs.push_back(WgradJob{dy, x, out, accs[i] != 0, np, cap});
+    jobs.push_back(checked_job("wgrad_gemm_multi", outs[i], dys[i], xs[i], accs[i] != 0, norms[i]));
+    any_norm = any_norm || jobs.back().nrm != nullptr;
   }
   SFT_TRACE(trace_name("wgrad.multi", (int)n));
   if (any_norm) SFT_TRACE("wgrad.norm_slots");

@@ -68,26 +68,26 @@ class Attention(nn.Module):
         if self.lora is None and self.use_rope and self.cp_group is None:
             # projection + RoPE (GEMM epilogue) + attention as one autograd node: the backward applies the inverse
             # rotation inside the attention kernels' dq / dK epilogues
-            # the o_proj backward computes the attention backward's delta in its dgrad epilogue (box: the hand-off)
-            box = {}
+            # the o_proj backward computes the attention backward's delta in its dgrad epilogue (link: the hand-off)
+            link = ops.AttnLink()
             a = ops.qkv_rope_attention(h, self.qkv_proj, rope_cs[0], rope_cs[1], cu_seqlens, max_seqlen,
-                                       c.num_attention_heads, c.num_key_value_heads, c.head_dim, delta_box=box)
-            return ops.attn_out_linear(a, self.o_proj, box)
+                                       c.num_attention_heads, c.num_key_value_heads, c.head_dim, link=link)
+            return ops.attn_out_linear(a, self.o_proj, link)
         if self.lora is not None and self.use_rope and self.cp_group is None:
             # the LoRA-widened qkv GEMM with the RoPE epilogue + attention as one node (inverse RoPE in the backward's
             # dq / dK epilogues), the plain composition where the HIP path does not apply
             a = ops.lora_qkv_rope_attention(h, self.qkv_proj, self.lora["qkv"], rope_cs[0], rope_cs[1], cu_seqlens,
                                             max_seqlen, c.num_attention_heads, c.num_key_value_heads, c.head_dim)
             return ops.lora_linear(a, self.o_proj, self.lora["o"])
-        pair = None
+        link = None
         if self.lora is None and self.use_rope:
             # projection + RoPE in one HIP GEMM (epilogue rotation) where the shapes allow
             qkv = ops.linear_rope(h, self.qkv_proj, rope_cs[0], rope_cs[1], c.num_attention_heads,
                                   c.num_key_value_heads, c.head_dim)
         else:
             # (a NoPE layer: the qkv node also issues o_proj's weight gradient, as one launch with its own)
-            pair = {} if (self.lora is None and not self.use_rope and self.cp_group is None) else None
-            qkv = (ops.qkv_in_linear(h, self.qkv_proj, pair) if self.lora is None
+            link = ops.AttnLink() if (self.lora is None and not self.use_rope and self.cp_group is None) else None
+            qkv = (ops.qkv_in_linear(h, self.qkv_proj, link) if self.lora is None
                    else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
             if self.use_rope:
                 qkv = ops.rope_(qkv, rope_cs[0], rope_cs[1], c.num_attention_heads, c.num_key_value_heads, c.head_dim)
@@ -96,11 +96,12 @@ class Attention(nn.Module):
             a = ring_attention(qkv, cu_seqlens, max_seqlen, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
                                self.cp_group, layout=self.cp_layout)
         else:
-            box = (pair if pair is not None else {}) if self.lora is None else None
+            if self.lora is None and link is None:
+                link = ops.AttnLink()
             a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, c.num_attention_heads, c.num_key_value_heads,
-                                    c.head_dim, delta_box=box)
-            if box is not None:
-                return ops.attn_out_linear(a, self.o_proj, box)
+                                    c.head_dim, link=link)
+            if link is not None:
+                return ops.attn_out_linear(a, self.o_proj, link)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
 
     def _forward_qk_norm(self, h, rope_cs, cu_seqlens, max_seqlen):
@@ -113,8 +114,8 @@ class Attention(nn.Module):
         nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         assert self.use_rope, "qk-norm layers rotate on every layer"
         plain = self.lora is None and self.cp_group is None
-        pair = {} if plain else None
-        qkv = (ops.qkv_in_linear(h, self.qkv_proj, pair) if self.lora is None
+        link = ops.AttnLink() if plain else None
+        qkv = (ops.qkv_in_linear(h, self.qkv_proj, link) if self.lora is None
                else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
         qkv = ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, rope_cs[0], rope_cs[1], nq, nkv, D,
                                 self.q_norm.eps)
@@ -122,9 +123,9 @@ class Attention(nn.Module):
             from ..parallel.context_parallel import ring_attention
             a = ring_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, self.cp_group, layout=self.cp_layout)
         else:
-            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, delta_box=pair)
-            if pair is not None:
-                return ops.attn_out_linear(a, self.o_proj, pair)
+            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, link=link)
+            if link is not None:
+                return ops.attn_out_linear(a, self.o_proj, link)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
 
 

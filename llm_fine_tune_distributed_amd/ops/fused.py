@@ -18,7 +18,7 @@ from __future__ import annotations
 import math
 import os
 import weakref
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -132,62 +132,61 @@ def _wgrad_mm(out: torch.Tensor, dy2d: torch.Tensor, x2d: torch.Tensor, accumula
     return False
 
 
+def _norm_slots(param: torch.Tensor) -> Optional[torch.Tensor]:
+    """The gradient-norm partial slots a weight-gradient launch fills for ``param`` (DDPEngine fused norm,
+    synchronising pass only): only with the parameter's last contribution of the pass."""
+    ns = getattr(param, "_sftamd_norm_slots", None)
+    return ns if (ns is not None and getattr(param, "_sftamd_remaining", 1) == 1) else None
+
+
+def _wgrad_landed(param: torch.Tensor, norm_done: bool) -> None:
+    """One contribution to ``param.main_grad`` has been issued (every launcher below ends here)."""
+    if norm_done:
+        param._sftamd_norm_done = True
+    param._sftamd_fresh = False
+    _weight_grad_done(param)
+
+
 def _accumulate_weight_grad(param: torch.Tensor, dy2d: torch.Tensor, x2d: torch.Tensor,
                             scale: Optional[torch.Tensor] = None):
-    """dW = dy^T @ x (optionally * scale). Accumulates into main_grad if present."""
+    """dW = dy^T @ x (optionally * scale), one launch, any dtype. Accumulates into main_grad if present."""
     mg = getattr(param, "main_grad", None)
     if scale is not None:
         x2d = x2d * scale.to(x2d.dtype)
-    if mg is not None:
-        fresh = getattr(param, "_sftamd_fresh", False)
-        if mg.dtype == dy2d.dtype:
-            # first contribution of the step: beta=0 GEMM, no zero-fill pass needed. Norm partials (DDPEngine
-            # fused norm, synchronising pass only) when this is the parameter's last contribution of the pass.
-            ns = getattr(param, "_sftamd_norm_slots", None)
-            if ns is not None and getattr(param, "_sftamd_remaining", 1) != 1:
-                ns = None
-            done = _wgrad_mm(mg, dy2d, x2d, accumulate=not fresh, norm=ns)
-            if done:
-                param._sftamd_norm_done = True
-        elif fresh:
-            mg.copy_(torch.mm(dy2d.t(), x2d))
-        else:
-            mg.add_(torch.mm(dy2d.t(), x2d).to(mg.dtype))
-        param._sftamd_fresh = False
-        _weight_grad_done(param)
-        return None
-    return torch.mm(dy2d.t(), x2d).to(param.dtype)
+    if mg is None:
+        return torch.mm(dy2d.t(), x2d).to(param.dtype)
+    fresh = getattr(param, "_sftamd_fresh", False)
+    norm_done = False
+    if mg.dtype == dy2d.dtype:
+        # first contribution of the step: beta=0 GEMM, no zero-fill pass needed
+        norm_done = _wgrad_mm(mg, dy2d, x2d, accumulate=not fresh, norm=_norm_slots(param))
+    elif fresh:
+        mg.copy_(torch.mm(dy2d.t(), x2d))
+    else:
+        mg.add_(torch.mm(dy2d.t(), x2d).to(mg.dtype))
+    _wgrad_landed(param, norm_done)
+    return None
 
 
 # Weight gradients in pairs as ONE 4-wave grid: the MLP's down projection defers its weight gradient to the gate_up
-# node, the attention's o_proj to the qkv + RoPE + attention node (per-call dicts link them), which then issue both in
-# one launch — MLP: 344 + 688 tiles = 4.03 rounds of 256 CUs instead of 1.34 + 2.69 with a partial last round each (a
-# partial round costs 0.75-1 of a full one: tools/debug/round_scaling.py, profiles/r6_gemm_routing.md); attention:
+# node, the attention's o_proj to the qkv + RoPE + attention node (MLPLink / AttnLink join them), which then issue both
+# in one launch — MLP: 344 + 688 tiles = 4.03 rounds of 256 CUs instead of 1.34 + 2.69 with a partial last round each
+# (a partial round costs 0.75-1 of a full one: tools/debug/round_scaling.py, profiles/r6_gemm_routing.md); attention:
 # 64 + 96 tiles split 3 ways = 2 rounds of third-tiles. SFTAMD_WGRAD_PAIR=0: off.
 _WGRAD_PAIR = os.environ.get("SFTAMD_WGRAD_PAIR", "1") == "1"
 
 
-def _job_ok(p, dy, x) -> bool:
-    """A weight gradient the 4-wave multi-problem launches take (bf16 main_grad, 256-multiple shapes, aligned rows)."""
+def _job_tiles(p, dy, x) -> Optional[int]:
+    """The 256 x 256 tile count of a weight gradient the 4-wave multi-problem launches take (HIP path, bf16 main_grad,
+    256-multiple shapes, aligned rows); None for any other job, which always launches on its own."""
     mg = getattr(p, "main_grad", None)
-    return (mg is not None and mg.dtype == torch.bfloat16 and mg.is_contiguous() and dy.dtype == torch.bfloat16
+    if not (dy.is_cuda and _ext.use_hip(dy) and x.shape[0] == dy.shape[0]
+            and mg is not None and mg.dtype == torch.bfloat16 and mg.is_contiguous() and dy.dtype == torch.bfloat16
             and x.dtype == torch.bfloat16 and dy.shape[1] % 256 == 0 and x.shape[1] % 256 == 0
             and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
-            and mg.data_ptr() % 16 == 0)
-
-
-def _pair_ok(p0, dy0, x0, p1, dy1, x1) -> bool:
-    one = _job_ok
-    if not (_WGRAD_PAIR and _WGRAD_MODE in ("auto", "") and dy0.is_cuda and _ext.use_hip(dy0)):
-        return False
-    T = dy0.shape[0]
-    if not (T % 128 == 0 and T >= 1024 and dy1.shape[0] == T and x0.shape[0] == T and x1.shape[0] == T):
-        return False
-    if not (one(p0, dy0, x0) and one(p1, dy1, x1)):
-        return False
-    t0 = (dy0.shape[1] // 256) * (x0.shape[1] // 256)
-    t1 = (dy1.shape[1] // 256) * (x1.shape[1] // 256)
-    return _pair_split(t0, t1, T) > 1 or (t0 + t1) % _CU_BUDGET <= t1
+            and mg.data_ptr() % 16 == 0):
+        return None
+    return (dy.shape[1] // 256) * (x.shape[1] // 256)
 
 
 def _pair_split(t0: int, t1: int, T: int) -> int:
@@ -204,30 +203,6 @@ def _pair_split(t0: int, t1: int, T: int) -> int:
         if cost is None or c < cost - 1e-9:
             best, cost = s, c
     return best
-
-
-def _accumulate_weight_grad_pair(p0, dy0, x0, p1, dy1, x1):
-    """_accumulate_weight_grad(p0, dy0, x0) and (p1, dy1, x1) — one wgrad_gemm_pair launch where it applies."""
-    if not _pair_ok(p0, dy0, x0, p1, dy1, x1):
-        _accumulate_weight_grad(p0, dy0, x0)
-        _accumulate_weight_grad(p1, dy1, x1)
-        return
-    split_all = _pair_split((dy0.shape[1] // 256) * (x0.shape[1] // 256), (dy1.shape[1] // 256) * (x1.shape[1] // 256),
-                            dy0.shape[0])
-
-    def slots(p):
-        ns = getattr(p, "_sftamd_norm_slots", None)
-        return ns if (ns is not None and getattr(p, "_sftamd_remaining", 1) == 1) else None
-
-    n0, n1 = slots(p0), slots(p1)
-    _ext.ops().wgrad_gemm_pair(p0.main_grad, dy0.contiguous(), x0, not getattr(p0, "_sftamd_fresh", False), n0,
-                               p1.main_grad, dy1.contiguous(), x1, not getattr(p1, "_sftamd_fresh", False), n1,
-                               split_all)
-    for p, ns in ((p0, n0), (p1, n1)):
-        if ns is not None:
-            p._sftamd_norm_done = True
-        p._sftamd_fresh = False
-        _weight_grad_done(p)
 
 
 # SFTAMD_WGRAD_CARRY=0: a layer's o_proj + qkv weight gradients launch on their own (2 rounds of third-tiles)
@@ -255,62 +230,128 @@ def _multi_split(total: int, T: int) -> int:
     return best
 
 
-def _multi_ok(jobs) -> bool:
-    p0, dy0, x0 = jobs[0]
-    if not (_WGRAD_PAIR and _WGRAD_MODE in ("auto", "") and dy0.is_cuda and _ext.use_hip(dy0)):
-        return False
-    T = dy0.shape[0]
-    if not (T % 128 == 0 and T >= 1024 and all(dy.shape[0] == T and x.shape[0] == T for _, dy, x in jobs)):
-        return False
-    if not all(_job_ok(p, dy, x) for p, dy, x in jobs):
-        return False
-    return sum((dy.shape[1] // 256) * (x.shape[1] // 256) for _, dy, x in jobs) >= _CU_BUDGET
+class _Launch(NamedTuple):
+    """One weight-gradient launch of a plan: jobs[first : first + count]. count 1: _accumulate_weight_grad (_wgrad_cfg
+    picks the kernel), 2: wgrad_gemm_pair, 3-4: wgrad_gemm_multi."""
+    first: int
+    count: int
+    split_all: int = 0   # a pair: every tile split this many ways over the tokens (0: whole rounds + hybrid leftover)
+    split_left: int = 0  # 3-4 jobs: the partial last round split this many ways (1: unsplit)
 
 
-def _accumulate_weight_grad_jobs(jobs):
-    """Weight gradients [(param, dy2d, x2d)] over the same tokens: ONE wgrad_gemm_multi launch for 3-4 of them (a
-    layer's down + gate_up with the next layer's o_proj + qkv: 1192 tiles = 4 whole rounds + a partial round of 168
-    tiles, against 4 rounds + 8 split tiles and a separate 2-round grid of third-tiles), pairs / single launches otherwise."""
-    if len(jobs) == 1:
+def _plan_wgrad(tiles, tokens) -> list:
+    """How the weight gradients of one backward node are grouped into launches — integers only. tiles[i]: job i's tile
+    count (_job_tiles; None = not a 4-wave multi-problem job), tokens[i]: its token count T.
+    A group of consecutive jobs shares a launch only when pairing is on (SFTAMD_WGRAD_PAIR, SFTAMD_WGRAD auto), every
+    job in it has a tile count and the same T, T % 128 == 0 and T >= 1024. Then 3-4 jobs that fill at least one round
+    of the CU budget are ONE launch (a layer's down + gate_up with the next layer's o_proj + qkv: 1192 tiles = 4 whole
+    rounds + a partial round of 168 tiles, against 4 rounds + 8 split tiles and a separate 2-round grid of
+    third-tiles); two jobs are a pair when every tile is split (_pair_split > 1) or the partial round falls in the
+    second problem (what the pair kernel takes). Everything else: the first two jobs, then the rest, planned alone."""
+    B = _CU_BUDGET
+
+    def shared(lo, hi):
+        T = tokens[lo]
+        return (_WGRAD_PAIR and _WGRAD_MODE in ("auto", "") and T % 128 == 0 and T >= 1024
+                and all(t is not None for t in tiles[lo:hi]) and all(t == T for t in tokens[lo:hi]))
+
+    def plan(lo, hi):
+        n = hi - lo
+        if n == 1:
+            return [_Launch(lo, 1)]
+        if n == 2:
+            if shared(lo, hi):
+                t0, t1 = tiles[lo], tiles[lo + 1]
+                split_all = _pair_split(t0, t1, tokens[lo])
+                if split_all > 1 or (t0 + t1) % B <= t1:
+                    return [_Launch(lo, 2, split_all=split_all)]
+            return [_Launch(lo, 1), _Launch(lo + 1, 1)]
+        if n <= 4 and shared(lo, hi) and sum(tiles[lo:hi]) >= B:
+            return [_Launch(lo, n, split_left=_multi_split(sum(tiles[lo:hi]), tokens[lo]))]
+        return plan(lo, lo + 2) + plan(lo + 2, hi)
+
+    return plan(0, len(tiles)) if tiles else []
+
+
+def _accumulate_weight_grad_jobs(jobs) -> None:
+    """Weight gradients [(param, dy2d, x2d)] of parameters with a main_grad, in the launches _plan_wgrad groups them
+    into."""
+    if len(jobs) == 1:  # (nothing to group: skip the planning)
         _accumulate_weight_grad(*jobs[0])
         return
-    if len(jobs) == 2:
-        _accumulate_weight_grad_pair(*jobs[0], *jobs[1])
-        return
-    if not _multi_ok(jobs):
-        _accumulate_weight_grad_jobs(jobs[:2])
-        _accumulate_weight_grad_jobs(jobs[2:])
-        return
-    T = jobs[0][1].shape[0]
-    total = sum((dy.shape[1] // 256) * (x.shape[1] // 256) for _, dy, x in jobs)
-    split_left = _multi_split(total, T)
+    for first, count, split_all, split_left in _plan_wgrad([_job_tiles(*j) for j in jobs],
+                                                           [dy.shape[0] for _, dy, _ in jobs]):
+        if count == 1:
+            _accumulate_weight_grad(*jobs[first])
+            continue
+        group = jobs[first:first + count]
+        norms = [_norm_slots(p) for p, _, _ in group]
+        accs = [not getattr(p, "_sftamd_fresh", False) for p, _, _ in group]
+        if count == 2:
+            (p0, dy0, x0), (p1, dy1, x1) = group
+            _ext.ops().wgrad_gemm_pair(p0.main_grad, dy0.contiguous(), x0, accs[0], norms[0],
+                                       p1.main_grad, dy1.contiguous(), x1, accs[1], norms[1], split_all)
+        else:
+            empty = group[0][1].new_empty(0, dtype=torch.float32)
+            _ext.ops().wgrad_gemm_multi([p.main_grad for p, _, _ in group], [dy.contiguous() for _, dy, _ in group],
+                                        [x for _, _, x in group], [int(a) for a in accs],
+                                        [n if n is not None else empty for n in norms], 0, split_left)
+        for (p, _, _), n in zip(group, norms):
+            _wgrad_landed(p, n is not None)
 
-    def slots(p):
-        ns = getattr(p, "_sftamd_norm_slots", None)
-        return ns if (ns is not None and getattr(p, "_sftamd_remaining", 1) == 1) else None
 
-    ns = [slots(p) for p, _, _ in jobs]
-    empty = jobs[0][1].new_empty(0, dtype=torch.float32)
-    _ext.ops().wgrad_gemm_multi([p.main_grad for p, _, _ in jobs], [dy.contiguous() for _, dy, _ in jobs],
-                                [x for _, _, x in jobs], [0 if getattr(p, "_sftamd_fresh", False) else 1 for p, _, _ in jobs],
-                                [n if n is not None else empty for n in ns], 0, split_left)
-    for (p, _, _), n in zip(jobs, ns):
-        if n is not None:
-            p._sftamd_norm_done = True
-        p._sftamd_fresh = False
-        _weight_grad_done(p)
+# ----------------------------------------------------------------------------- hand-off between autograd nodes
+class MLPLink:
+    """Joins the two projection nodes of one swiglu_mlp call (and, through wgrad_carry_scope, the next layer's
+    attention) so that their weight gradients run as one launch."""
+    __slots__ = ("gate_up_runs", "down_job", "attn_jobs")
+
+    def __init__(self):
+        # written by gate_up's forward (PairedLinearFn: its backward will run); read by whoever would defer a job to it
+        self.gate_up_runs = False
+        # (param, dy2d, x2d) written by down's backward (SwiGLULinearFn); taken by gate_up's backward
+        self.down_job = None
+        # [o_proj job, qkv job] written by the next layer's qkv backward (_carry_or_launch); taken by gate_up's backward
+        self.attn_jobs = None
+
+
+class AttnLink:
+    """Joins the nodes of one attention call, a fresh one per layer call: the qkv node (QKVRopeAttnFn, or
+    PairedLinearFn on a NoPE / qk-norm layer), the attention node (QKVRopeAttnFn / FlashAttnFn) and o_proj."""
+    __slots__ = ("delta_ok", "qkv_takes_o_wgrad", "o_job", "delta")
+
+    def __init__(self):
+        # written by the attention node's forward (the HIP flash forward ran, head_dim 128); read by attn_out_linear and
+        # o_proj's backward (AttnOutLinearFn): the delta hand-off is allowed
+        self.delta_ok = False
+        # written by the qkv node's forward (its backward will run); read by o_proj's backward before it defers o_job
+        self.qkv_takes_o_wgrad = False
+        # (param, dy2d, x2d) written by o_proj's backward; taken by the qkv node's backward
+        self.o_job = None
+        # (delta, dO data_ptr, dO shape) written by o_proj's backward; taken by the attention node's (_take_delta)
+        self.delta = None
+
+
+def _take(link, field: str):
+    """link.field, cleared (None when there is no link)."""
+    if link is None:
+        return None
+    got = getattr(link, field)
+    setattr(link, field, None)
+    return got
 
 
 # The hand-off of a layer's attention weight gradients to the previous layer's MLP launch: CausalLM.forward opens a
-# scope; swiglu_mlp leaves its (armed) dict in it and the next layer's attention node takes that dict, deposits its
-# o_proj + qkv weight-gradient jobs there in its backward (which always runs before the previous layer's gate_up
-# backward: that node's output feeds this layer), and the gate_up node launches all four at once.
-_CARRY = None
+# scope; swiglu_mlp leaves its MLPLink in it (when its gate_up backward will run) and the next layer's qkv node takes
+# that link, deposits its o_proj + qkv weight-gradient jobs there in its backward (which always runs before the
+# previous layer's gate_up backward: that node's output feeds this layer), and the gate_up node launches all four at
+# once.
+_CARRY = None  # inside a scope: [the MLPLink on offer, or None]
 
 
 class wgrad_carry_scope:
     """`with wgrad_carry_scope(enabled):` around the decoder-layer loop of one forward (no activation checkpointing:
-    recomputed layers would arm dicts whose nodes never run)."""
+    recomputed layers would offer links whose nodes never run)."""
 
     def __init__(self, enabled: bool = True):
         self.enabled = bool(enabled and _WGRAD_CARRY and _WGRAD_PAIR and torch.is_grad_enabled())
@@ -318,7 +359,7 @@ class wgrad_carry_scope:
     def __enter__(self):
         global _CARRY
         self.prev = _CARRY
-        _CARRY = {"mlp": None} if self.enabled else None
+        _CARRY = [None] if self.enabled else None
         return self
 
     def __exit__(self, *exc):
@@ -327,26 +368,46 @@ class wgrad_carry_scope:
         return False
 
 
-def _carry_put(box: Optional[dict]) -> None:
+def _carry_put(link: Optional[MLPLink]) -> None:
     if _CARRY is not None:
-        _CARRY["mlp"] = box if (box is not None and box.get("armed")) else None
+        _CARRY[0] = link if (link is not None and link.gate_up_runs) else None
 
 
-def _carry_take() -> Optional[dict]:
+def _carry_take() -> Optional[MLPLink]:
     if _CARRY is None:
         return None
-    box, _CARRY["mlp"] = _CARRY["mlp"], None
-    return box
+    link, _CARRY[0] = _CARRY[0], None
+    return link
 
 
-def _carry_or_launch(carry: Optional[dict], jobs) -> None:
-    """The attention node's weight-gradient jobs: into the previous layer's MLP dict when it will launch them with its
-    own (armed, 4-problem launch eligible), else now."""
-    if (carry is not None and carry.get("armed") and "attn" not in carry and len(jobs) == 2
+def _carry_or_launch(carry: Optional[MLPLink], jobs) -> None:
+    """The qkv node's weight-gradient jobs: to the previous layer's MLP link when its gate_up backward will launch
+    them with its own (4-problem launch eligible), else now."""
+    if (carry is not None and carry.gate_up_runs and carry.attn_jobs is None and len(jobs) == 2
             and all(getattr(p, "main_grad", None) is not None for p, _, _ in jobs)):
-        carry["attn"] = jobs
+        carry.attn_jobs = jobs
         return
     _accumulate_weight_grad_jobs(jobs)
+
+
+def _proj_backward(needs, w, dy2d, x2d, x_shape, dgrad=None, pending=None, extra=None, sink=None):
+    """The backward tail every projection node y = x W^T shares (needs = ctx.needs_input_grad: x first, then W).
+    Returns (dx, dw). dx = dgrad(dy2d, w) (dgrad_mm unless the node has a fused variant) viewed as x_shape, issued
+    first. Then the weight gradients:
+    this node's own goes to autograd as ``dw`` when the parameter has no main_grad; else its job (w, dy2d, x2d) joins
+    ``pending`` (the job the consumer node deferred to this one) in front and ``extra`` (jobs carried from the next
+    layer) behind, and ``sink(jobs)`` takes the list: _accumulate_weight_grad_jobs, unless the node defers or carries."""
+    dx = (dgrad or dgrad_mm)(dy2d, w).view(x_shape) if needs[0] else None
+    jobs = [pending] if pending is not None else []
+    dw = None
+    if needs[1] and getattr(w, "main_grad", None) is not None:
+        jobs.append((w, dy2d, x2d))
+    elif needs[1]:
+        dw = _accumulate_weight_grad(w, dy2d, x2d)
+    jobs += extra or []
+    if jobs:
+        (sink or _accumulate_weight_grad_jobs)(jobs)
+    return dx, dw
 
 
 def _accumulate_small_grad(param: torch.Tensor, g: torch.Tensor):
@@ -425,14 +486,8 @@ class LinearFn(Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        w = ctx.weight
-        dy2d = dy.reshape(-1, dy.shape[-1])
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = dgrad_mm(dy2d, w).view(*dy.shape[:-1], w.shape[1])
-        if ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dy2d, x.reshape(-1, x.shape[-1]))
-        return dx, dw
+        return _proj_backward(ctx.needs_input_grad, ctx.weight, dy.reshape(-1, dy.shape[-1]),
+                              x.reshape(-1, x.shape[-1]), x.shape)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -440,62 +495,53 @@ def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 
 class PairedLinearFn(Function):
-    """y = x W^T (LinearFn) for a projection whose CONSUMER defers its own weight gradient here through `box[key]`:
-    the MLP's gate_up (the down projection, SwiGLULinearFn, leaves "down") and a NoPE layer's qkv (o_proj,
-    AttnOutLinearFn, leaves "o_wgrad"). The backward issues both weight gradients as one launch
-    (_accumulate_weight_grad_pair) after this node's input gradient."""
+    """y = x W^T (LinearFn) for a projection whose CONSUMER defers its own weight gradient here through `link`: the
+    MLP's gate_up (an MLPLink: the down projection, SwiGLULinearFn, leaves down_job) and the qkv of a NoPE / qk-norm
+    layer (an AttnLink: o_proj, AttnOutLinearFn, leaves o_job). The backward issues both weight gradients as one launch
+    after this node's input gradient — gate_up together with the jobs carried from the next layer's attention, qkv
+    unless the previous layer's MLP (`carry`) takes them."""
 
     @staticmethod
-    def forward(ctx, x, weight, box, key, arm, carry=None):
+    def forward(ctx, x, weight, link, carry=None):
         ctx.save_for_backward(x)
         ctx.weight = weight
-        ctx.box = box
-        ctx.key = key
+        ctx.link = link
         ctx.carry = carry
         if weight.requires_grad:  # this node's backward will run: the consumer may leave its weight gradient to it
-            box[arm] = True
+            if isinstance(link, MLPLink):
+                link.gate_up_runs = True
+            else:
+                link.qkv_takes_o_wgrad = True
         x2d = x.reshape(-1, x.shape[-1])
         return _as_output(fwd_gemm(x2d, weight), x.shape[:-1])
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        w = ctx.weight
+        w, link = ctx.weight, ctx.link
         dy2d = dy.reshape(-1, dy.shape[-1])
         x2d = x.reshape(-1, x.shape[-1])
-        pending = ctx.box.pop(ctx.key, None)
-        extra = ctx.box.pop("attn", None)  # the next layer's o_proj + qkv jobs (_carry_or_launch)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = dgrad_mm(dy2d, w).view(*dy.shape[:-1], w.shape[1])
-        jobs = [pending] if pending is not None else []
-        if ctx.needs_input_grad[1] and getattr(w, "main_grad", None) is not None:
-            jobs.append((w, dy2d, x2d))
-        elif ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dy2d, x2d)
-        if ctx.carry is not None and ctx.key == "o_wgrad":  # a NoPE layer's qkv: the previous layer's MLP may take them
-            if jobs:
-                _carry_or_launch(ctx.carry, jobs)
+        if isinstance(link, MLPLink):
+            dx, dw = _proj_backward(ctx.needs_input_grad, w, dy2d, x2d, x.shape,
+                                    pending=_take(link, "down_job"), extra=_take(link, "attn_jobs"))
         else:
-            if jobs:
-                _accumulate_weight_grad_jobs(jobs + (extra or []))
-            elif extra:
-                _accumulate_weight_grad_jobs(extra)
-        return dx, dw, None, None, None, None
+            dx, dw = _proj_backward(ctx.needs_input_grad, w, dy2d, x2d, x.shape,
+                                    pending=_take(link, "o_job"), sink=lambda jobs: _carry_or_launch(ctx.carry, jobs))
+        return dx, dw, None, None
 
 
-def mlp_in_linear(x: torch.Tensor, weight: torch.Tensor, box: Optional[dict]) -> torch.Tensor:
-    """gate_up(x) whose backward also issues the down projection's weight gradient (swiglu_linear with `box`)."""
-    if box is not None and _ext.use_hip(x):
-        return PairedLinearFn.apply(x, weight, box, "down", "armed")
+def mlp_in_linear(x: torch.Tensor, weight: torch.Tensor, link: Optional[MLPLink]) -> torch.Tensor:
+    """gate_up(x) whose backward also issues the down projection's weight gradient (swiglu_linear with `link`)."""
+    if link is not None and _ext.use_hip(x):
+        return PairedLinearFn.apply(x, weight, link)
     return LinearFn.apply(x, weight)
 
 
-def qkv_in_linear(x: torch.Tensor, weight: torch.Tensor, box: Optional[dict]) -> torch.Tensor:
-    """qkv(x) of a NoPE layer whose backward also issues o_proj's weight gradient (attn_out_linear with `box`) — or
-    hands both to the previous layer's MLP launch (wgrad_carry_scope)."""
-    if box is not None and _WGRAD_PAIR and _ext.use_hip(x):
-        return PairedLinearFn.apply(x, weight, box, "o_wgrad", "wgrad_pair", _carry_take())
+def qkv_in_linear(x: torch.Tensor, weight: torch.Tensor, link: Optional[AttnLink]) -> torch.Tensor:
+    """qkv(x) of a NoPE / qk-norm layer whose backward also issues o_proj's weight gradient (attn_out_linear with
+    `link`) — or hands both to the previous layer's MLP launch (wgrad_carry_scope)."""
+    if link is not None and _WGRAD_PAIR and _ext.use_hip(x):
+        return PairedLinearFn.apply(x, weight, link, _carry_take())
     return LinearFn.apply(x, weight)
 
 
@@ -515,37 +561,36 @@ def _delta_ok(dy2d: torch.Tensor, w: torch.Tensor, a2d: torch.Tensor) -> bool:
 class AttnOutLinearFn(Function):
     """The attention output projection y = a W_o^T behind a fused attention node (QKVRopeAttnFn / FlashAttnFn). Its
     backward computes dO = dy W_o on the 4-wave kernel with flash attention's delta = rowsum(dO . a) per head in the
-    epilogue (dgrad_gemm_delta: `a` is this node's saved input, the attention output) and leaves it in `box` for the
+    epilogue (dgrad_gemm_delta: `a` is this node's saved input, the attention output) and leaves it in `link` for the
     attention node, whose backward then skips its delta kernel (a full re-read of dO and O, ~13 us per layer at
     16 x 512). The attention node checks that the gradient it receives IS that dO (same storage) before using it."""
 
     @staticmethod
-    def forward(ctx, x, weight, box):
+    def forward(ctx, x, weight, link):
         ctx.save_for_backward(x)
         ctx.weight = weight
-        ctx.box = box
+        ctx.link = link
         x2d = x.reshape(-1, x.shape[-1])
         return _as_output(fwd_gemm(x2d, weight), x.shape[:-1])
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        w = ctx.weight
-        dy2d = dy.reshape(-1, dy.shape[-1])
+        w, link = ctx.weight, ctx.link
         x2d = x.reshape(-1, x.shape[-1])
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            if ctx.box.get("armed") and _delta_ok(dy2d, w, x2d):
-                d2d, delta = _ext.ops().dgrad_gemm_delta(dy2d, w, x2d)
-                ctx.box["delta"] = (delta, d2d.data_ptr(), d2d.shape)
-            else:
-                d2d = dgrad_mm(dy2d, w)
-            dx = d2d.view(*dy.shape[:-1], w.shape[1])
-        if ctx.needs_input_grad[1]:
-            if ctx.box.get("wgrad_pair") and getattr(w, "main_grad", None) is not None:
-                ctx.box["o_wgrad"] = (w, dy2d, x2d)  # issued with qkv's (QKVRopeAttnFn.backward)
-            else:
-                dw = _accumulate_weight_grad(w, dy2d, x2d)
+
+        def dgrad(dy2d, w):
+            if not (link.delta_ok and _delta_ok(dy2d, w, x2d)):
+                return dgrad_mm(dy2d, w)
+            d2d, delta = _ext.ops().dgrad_gemm_delta(dy2d, w, x2d)
+            link.delta = (delta, d2d.data_ptr(), d2d.shape)
+            return d2d
+
+        def defer(jobs):  # issued with qkv's (QKVRopeAttnFn / PairedLinearFn backward)
+            link.o_job, = jobs
+
+        dx, dw = _proj_backward(ctx.needs_input_grad, w, dy.reshape(-1, dy.shape[-1]), x2d, x.shape,
+                                dgrad=dgrad, sink=defer if link.qkv_takes_o_wgrad else None)
         return dx, dw, None
 
 
@@ -553,20 +598,18 @@ class AttnOutLinearFn(Function):
 _DELTA_FUSED = os.environ.get("SFTAMD_ATTN_DELTA", "1") != "0"
 
 
-def attn_out_linear(a: torch.Tensor, weight: torch.Tensor, box: Optional[dict]) -> torch.Tensor:
-    """o_proj(a) for `a` from qkv_rope_attention / flash_attention called with the same `box` (a fresh dict per
+def attn_out_linear(a: torch.Tensor, weight: torch.Tensor, link: Optional[AttnLink]) -> torch.Tensor:
+    """o_proj(a) for `a` from qkv_rope_attention / flash_attention called with the same `link` (a fresh AttnLink per
     layer call): the delta hand-off above when the HIP paths apply, linear() otherwise."""
-    if _DELTA_FUSED and box is not None and box.get("armed") and _ext.use_hip(a):
-        return AttnOutLinearFn.apply(a, weight, box)
+    if _DELTA_FUSED and link is not None and link.delta_ok and _ext.use_hip(a):
+        return AttnOutLinearFn.apply(a, weight, link)
     return LinearFn.apply(a, weight)
 
 
-def _take_delta(box: Optional[dict], dout: torch.Tensor, n_q: int):
+def _take_delta(link: Optional[AttnLink], dout: torch.Tensor, n_q: int):
     """The delta AttnOutLinearFn left for this attention node, if the incoming gradient is the dO it computed it for
     (the same storage and shape: no other consumer of the attention output added into it)."""
-    if box is None:
-        return None
-    got = box.pop("delta", None)
+    got = _take(link, "delta")
     if got is None:
         return None
     delta, ptr, shape = got
@@ -641,38 +684,37 @@ def dgrad_mm(dy2d: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 class SwiGLULinearFn(Function):
     """y = swiglu(gu) @ W^T — the MLP down projection with its SwiGLU input. Backward: ONE
     HIP GEMM dgu = swiglu_bwd(dy @ W, gu) with the SwiGLU backward in the epilogue (the [M, I] dact is never
-    written), plus the weight gradient from the saved activation."""
+    written), plus the weight gradient from the saved activation. `act`: swiglu(gu) when the producer of gu wrote it
+    already (GateUpActFn: then neither SwiGLU pass runs as a separate kernel); `link`: see mlp_in_linear."""
 
     @staticmethod
-    def forward(ctx, gu, weight, box=None):
-        act = _ext.ops().swiglu_fwd(gu)
+    def forward(ctx, gu, weight, link=None, act=None):
+        if act is None:
+            act = _ext.ops().swiglu_fwd(gu)
         ctx.save_for_backward(gu, act)
         ctx.weight = weight
-        ctx.box = box
+        ctx.link = link
         a2d = act.reshape(-1, act.shape[-1])
         return _as_output(fwd_gemm(a2d, weight), gu.shape[:-1])
 
     @staticmethod
     def backward(ctx, dy):
         gu, act = ctx.saved_tensors
-        w = ctx.weight
-        dy2d = dy.reshape(-1, dy.shape[-1]).contiguous()
+        link = ctx.link
         gu2d = gu.reshape(-1, gu.shape[-1])
-        dgu = dw = None
-        if ctx.needs_input_grad[0]:
+
+        def dgrad(dy2d, w):
             if _dgrad_ok(dy2d, w) and gu2d.is_contiguous():
-                dgu = _ext.ops().dgrad_gemm(dy2d, w, gu2d, _dgrad_cfg(dy2d, swiglu=True))
-            else:
-                dgu = _ext.ops().swiglu_bwd(torch.mm(dy2d, w), gu2d)
-            dgu = dgu.view(gu.shape)
-        if ctx.needs_input_grad[1]:
-            a2d = act.reshape(-1, act.shape[-1])
-            box = ctx.box
-            if box is not None and box.get("armed") and getattr(w, "main_grad", None) is not None:
-                box["down"] = (w, dy2d, a2d)  # issued together with gate_up's (MLPInLinearFn.backward)
-            else:
-                dw = _accumulate_weight_grad(w, dy2d, a2d)
-        return dgu, dw, None
+                return _ext.ops().dgrad_gemm(dy2d, w, gu2d, _dgrad_cfg(dy2d, swiglu=True))
+            return swiglu_bwd(torch.mm(dy2d, w), gu2d)
+
+        def defer(jobs):  # issued together with gate_up's (PairedLinearFn.backward)
+            link.down_job, = jobs
+
+        dgu, dw = _proj_backward(ctx.needs_input_grad, ctx.weight, dy.reshape(-1, dy.shape[-1]).contiguous(),
+                                 act.reshape(-1, act.shape[-1]), gu.shape, dgrad=dgrad,
+                                 sink=defer if (link is not None and link.gate_up_runs) else None)
+        return dgu, dw, None, None
 
 
 _SWIGLU_DOWN = True  # (a test seam: tests/test_model_gpu.py switches the MLP split off)
@@ -684,11 +726,11 @@ def fuse_swiglu_down() -> bool:
     return _SWIGLU_DOWN and _TN_MODE not in ("1", "swiglu")
 
 
-def swiglu_linear(gu: torch.Tensor, weight: torch.Tensor, box: Optional[dict] = None) -> torch.Tensor:
-    """linear(swiglu(gu), weight) with the fused backward where the HIP kernels apply. box: shared with the
+def swiglu_linear(gu: torch.Tensor, weight: torch.Tensor, link: Optional[MLPLink] = None) -> torch.Tensor:
+    """linear(swiglu(gu), weight) with the fused backward where the HIP kernels apply. link: shared with the
     mlp_in_linear that produced gu (the two weight gradients then run as one launch)."""
     if _SWIGLU_DOWN and _ext.use_hip(gu) and gu.dtype == torch.bfloat16 and gu.is_contiguous():
-        return SwiGLULinearFn.apply(gu, weight, box)
+        return SwiGLULinearFn.apply(gu, weight, link)
     return linear(swiglu(gu), weight)
 
 
@@ -833,15 +875,7 @@ class SwiGLUFn(Function):
     @staticmethod
     def backward(ctx, dy):
         (gu,) = ctx.saved_tensors
-        if _ext.use_hip(gu):
-            return _ext.ops().swiglu_bwd(dy.contiguous(), gu)
-        g, u = gu.float().chunk(2, dim=-1)
-        sg = torch.sigmoid(g)
-        silu = g * sg
-        dyf = dy.float()
-        dg = dyf * u * (sg * (1 + g * (1 - sg)))
-        du = dyf * silu
-        return torch.cat([dg, du], dim=-1).to(gu.dtype)
+        return swiglu_bwd(dy, gu)
 
 
 def swiglu(gate_up: torch.Tensor) -> torch.Tensor:
@@ -864,13 +898,14 @@ def _tn_ok(x2d: torch.Tensor, w: torch.Tensor) -> bool:
             and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and w.is_contiguous() and w.shape[0] % 256 == 0)
 
 
-def _tn_cfg(M: int, N: int, K: int = 64) -> int:
-    """Forward GEMM with an epilogue (qkv + RoPE): the ping-pong 8-phase schedule (cfg 11, csrc/gemm_tn.hip: the two
-    wave rows one barrier apart, transposed-C epilogue) wherever N % 256 == 0 — 2-6 % faster than the BK64 ring (cfg 2)
-    on every SmolLM3 shape (profiles/r2_gemm_pingpong.md). The persistent row-contiguous kernel (cfg 61) is faster in
-    isolation (0.121 vs 0.131 ms) but slower in the step: 137 vs 106 us per call, its 384 tiles are 1.5 rounds of one
-    workgroup per CU and the cos / sin loads of its epilogue wait behind the next tile's DMA (profiles/r5_gemm_fwd.md)."""
-    return 11 if N % 256 == 0 else 2
+def _tn_cfg() -> int:
+    """Forward GEMM with an epilogue (qkv + RoPE; every caller requires N % 256 == 0): the ping-pong 8-phase schedule
+    (cfg 11, csrc/gemm_tn.hip: the two wave rows one barrier apart, transposed-C epilogue) — 2-6 % faster than the
+    BK64 ring (cfg 2) on every SmolLM3 shape (profiles/r2_gemm_pingpong.md). The persistent row-contiguous kernel
+    (cfg 61) is faster in isolation (0.121 vs 0.131 ms) but slower in the step: 137 vs 106 us per call, its 384 tiles
+    are 1.5 rounds of one workgroup per CU and the cos / sin loads of its epilogue wait behind the next tile's DMA
+    (profiles/r5_gemm_fwd.md)."""
+    return 11
 
 
 class GateUpSwiGLUFn(Function):
@@ -901,10 +936,9 @@ class GateUpSwiGLUFn(Function):
 
 def _tn_swiglu_cfg(weight: torch.Tensor) -> int:
     """gate_up + SwiGLU epilogue (SFTAMD_TN=swiglu / 1): the persistent 4-wave kernel where it applies (0.669 vs
-    0.705 ms for hipBLASLt + the SwiGLU kernel at M = 8192, profiles/r4_gemm_fwd.md), else the ping-pong kernel."""
-    if weight.shape[0] % 256 == 0 and weight.shape[1] % 128 == 0:
-        return _ROWC_CFG
-    return 11 if weight.shape[0] % 256 == 0 else 5
+    0.705 ms for hipBLASLt + the SwiGLU kernel at M = 8192, profiles/r4_gemm_fwd.md), else the ping-pong kernel (both
+    take N % 256 == 0 only: linear_swiglu and swiglu_mlp require it)."""
+    return _ROWC_CFG if weight.shape[1] % 128 == 0 else 11
 
 
 def linear_swiglu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -917,7 +951,7 @@ def linear_swiglu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 class GateUpActFn(Function):
     """(gu, act) = (x [Wg; Wu]^T, silu(gate) * up) from ONE HIP GEMM with the SwiGLU epilogue; act is
-    non-differentiable here because the consumer (SwiGLUDownFn) returns the gradient of gu directly."""
+    non-differentiable here because the consumer (SwiGLULinearFn, given act) returns the gradient of gu directly."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -934,43 +968,7 @@ class GateUpActFn(Function):
     @staticmethod
     def backward(ctx, dgu, _dact):
         (x2d,) = ctx.saved_tensors
-        w = ctx.weight
-        dgu2d = dgu.reshape(-1, dgu.shape[-1])
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = dgrad_mm(dgu2d, w).view(ctx.x_shape)
-        if ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dgu2d, x2d)
-        return dx, dw
-
-
-class SwiGLUDownFn(Function):
-    """y = act @ W^T for an act produced together with gu (GateUpActFn); backward = the fused
-    dgu = swiglu_bwd(dy @ W, gu) GEMM of SwiGLULinearFn — neither SwiGLU pass runs as a separate kernel."""
-
-    @staticmethod
-    def forward(ctx, gu, act, weight):
-        ctx.save_for_backward(gu, act)
-        ctx.weight = weight
-        a2d = act.reshape(-1, act.shape[-1])
-        return _as_output(fwd_gemm(a2d, weight), gu.shape[:-1])
-
-    @staticmethod
-    def backward(ctx, dy):
-        gu, act = ctx.saved_tensors
-        w = ctx.weight
-        dy2d = dy.reshape(-1, dy.shape[-1]).contiguous()
-        gu2d = gu.reshape(-1, gu.shape[-1])
-        dgu = dw = None
-        if ctx.needs_input_grad[0]:
-            if _dgrad_ok(dy2d, w):
-                dgu = _ext.ops().dgrad_gemm(dy2d, w, gu2d, _dgrad_cfg(dy2d, swiglu=True))
-            else:
-                dgu = _ext.ops().swiglu_bwd(torch.mm(dy2d, w), gu2d)
-            dgu = dgu.view(gu.shape)
-        if ctx.needs_input_grad[2]:
-            dw = _accumulate_weight_grad(w, dy2d, act.reshape(-1, act.shape[-1]))
-        return dgu, None, dw
+        return _proj_backward(ctx.needs_input_grad, ctx.weight, dgu.reshape(-1, dgu.shape[-1]), x2d, ctx.x_shape)
 
 
 def swiglu_mlp(h: torch.Tensor, w_gate_up: torch.Tensor, w_down: torch.Tensor) -> torch.Tensor:
@@ -986,11 +984,11 @@ def swiglu_mlp(h: torch.Tensor, w_gate_up: torch.Tensor, w_down: torch.Tensor) -
     if (fused_gu and _SWIGLU_DOWN and _tn_ok(h2d, w_gate_up) and w_gate_up.shape[0] % 256 == 0
             and (w_gate_up.shape[0] // 2) % 128 == 0):
         gu, act = GateUpActFn.apply(h, w_gate_up)
-        return SwiGLUDownFn.apply(gu, act, w_down)
+        return SwiGLULinearFn.apply(gu, w_down, None, act)
     if fuse_swiglu_down():
-        box = {} if _WGRAD_PAIR else None
-        y = swiglu_linear(mlp_in_linear(h, w_gate_up, box), w_down, box)
-        _carry_put(box)  # the next layer's attention may leave its weight gradients to this MLP's launch
+        link = MLPLink() if _WGRAD_PAIR else None
+        y = swiglu_linear(mlp_in_linear(h, w_gate_up, link), w_down, link)
+        _carry_put(link)  # the next layer's attention may leave its weight gradients to this MLP's launch
         return y
     return linear(linear_swiglu(h, w_gate_up), w_down)
 
@@ -1001,7 +999,7 @@ class QKVRopeFn(Function):
     @staticmethod
     def forward(ctx, x, weight, cos, sin, n_q, n_kv, head_dim):
         x2d = x.reshape(-1, x.shape[-1])
-        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg(x2d.shape[0], weight.shape[0], x2d.shape[1]))
+        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
         ctx.save_for_backward(x2d, cos, sin)
         ctx.weight = weight
         ctx.dims = (n_q, n_kv, head_dim)
@@ -1011,24 +1009,25 @@ class QKVRopeFn(Function):
     @staticmethod
     def backward(ctx, dqkv):
         x2d, cos, sin = ctx.saved_tensors
-        w = ctx.weight
         n_q, n_kv, hd = ctx.dims
         dqkv = dqkv.contiguous()
         _rope_inplace(dqkv, cos, sin, n_q, n_kv, hd, inverse=True)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = dgrad_mm(dqkv, w).view(ctx.x_shape)
-        if ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dqkv, x2d)
+        dx, dw = _proj_backward(ctx.needs_input_grad, ctx.weight, dqkv, x2d, ctx.x_shape)
         return dx, dw, None, None, None, None, None
+
+
+def _rope_epilogue_ok(x2d, weight, cos, sin, head_dim) -> bool:
+    """What the RoPE epilogue of gemm_tn_rope takes, on top of its caller's own GEMM shape rule (_tn_ok, or the LoRA
+    wide guard): head_dim 128, whole 256 x 256 tiles, and contiguous fp32 cos / sin tables [M, 64]."""
+    return (head_dim == 128 and _ext.use_hip(x2d) and x2d.shape[0] % 256 == 0 and weight.shape[0] % 256 == 0
+            and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+            and cos.shape == (x2d.shape[0], 64))
 
 
 def linear_rope(x, weight, cos, sin, n_q, n_kv, head_dim):
     """rope_(linear(x, W_qkv)) on the packed [M, (n_q + 2 n_kv) * head_dim] layout."""
     x2d = x.reshape(-1, x.shape[-1])
-    if (_TN_MODE in ("1", "rope") and head_dim == 128 and _tn_ok(x2d, weight) and cos.dtype == torch.float32
-            and cos.is_contiguous()
-            and sin.is_contiguous() and cos.shape == (x2d.shape[0], 64)):
+    if _TN_MODE in ("1", "rope") and _tn_ok(x2d, weight) and _rope_epilogue_ok(x2d, weight, cos, sin, head_dim):
         return QKVRopeFn.apply(x, weight, cos, sin, n_q, n_kv, head_dim)
     return rope_(linear(x, weight), cos, sin, n_q, n_kv, head_dim)
 
@@ -1126,15 +1125,15 @@ def qk_norm_rope_(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps):
 # ----------------------------------------------------------------------------- attention
 class FlashAttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, box=None):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None):
         ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal)
-        ctx.box = box
+        ctx.link = link
         if _ext.use_hip(qkv):
             out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
             ctx.save_for_backward(qkv, cu_seqlens, out, lse)
             ctx.hip = True
-            if box is not None and head_dim == 128:
-                box["armed"] = True
+            if link is not None and head_dim == 128:
+                link.delta_ok = True
         else:
             out = ref.attention(qkv, n_q, n_kv, head_dim, cu_seqlens, scale, causal)
             ctx.save_for_backward(qkv, cu_seqlens)
@@ -1147,7 +1146,7 @@ class FlashAttnFn(Function):
         if ctx.hip:
             qkv, cu, out, lse = ctx.saved_tensors
             dqkv = _ext.ops().flash_bwd(dout.contiguous(), qkv, out, lse, cu, max_seqlen, n_q, n_kv, hd, scale, causal,
-                                        _take_delta(ctx.box, dout, n_q))
+                                        _take_delta(ctx.link, dout, n_q))
         else:
             qkv, cu = ctx.saved_tensors
             with torch.enable_grad():
@@ -1158,12 +1157,12 @@ class FlashAttnFn(Function):
         return dqkv, None, None, None, None, None, None, None, None
 
 
-def flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True, delta_box=None):
-    """delta_box: a fresh dict shared with attn_out_linear (the o_proj on this output): the o_proj backward computes
+def flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True, link=None):
+    """link: a fresh AttnLink shared with attn_out_linear (the o_proj on this output): the o_proj backward computes
     the attention backward's delta in its dgrad epilogue."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     return FlashAttnFn.apply(qkv, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim, float(scale), bool(causal),
-                             delta_box)
+                             link)
 
 
 class QKVRopeAttnFn(Function):
@@ -1173,17 +1172,16 @@ class QKVRopeAttnFn(Function):
     QKVRopeFn + FlashAttnFn (tests/test_model_gpu.py)."""
 
     @staticmethod
-    def forward(ctx, x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, box=None,
+    def forward(ctx, x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None,
                 carry=None):
-        ctx.box = box
+        ctx.link = link
         ctx.carry = carry
-        if box is not None:
-            box["armed"] = True
+        if link is not None:
+            link.delta_ok = True
             if _WGRAD_PAIR and weight.requires_grad:  # this node's backward runs: o_proj may leave its wgrad here
-                box["wgrad_pair"] = True
+                link.qkv_takes_o_wgrad = True
         x2d = x.reshape(-1, x.shape[-1])
-        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim,
-                                      _tn_cfg(x2d.shape[0], weight.shape[0], x2d.shape[1]))
+        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
         out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
         ctx.save_for_backward(x2d, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.weight = weight
@@ -1195,21 +1193,11 @@ class QKVRopeAttnFn(Function):
     def backward(ctx, dout):
         x2d, qkv, cu, out, lse, cos, sin = ctx.saved_tensors
         max_seqlen, n_q, n_kv, hd, scale, causal = ctx.dims
-        w = ctx.weight
         dqkv = _ext.ops().flash_bwd_rope(dout.contiguous(), qkv, out, lse, cu, max_seqlen, n_q, n_kv, hd, scale, causal,
-                                         cos, sin, _take_delta(ctx.box, dout, n_q))
+                                         cos, sin, _take_delta(ctx.link, dout, n_q))
         del qkv, out, lse
-        pending = ctx.box.pop("o_wgrad", None) if ctx.box is not None else None
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = dgrad_mm(dqkv, w).view(ctx.x_shape)
-        jobs = [pending] if pending is not None else []
-        if ctx.needs_input_grad[1] and getattr(w, "main_grad", None) is not None:
-            jobs.append((w, dqkv, x2d))
-        elif ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dqkv, x2d)
-        if jobs:
-            _carry_or_launch(ctx.carry, jobs)
+        dx, dw = _proj_backward(ctx.needs_input_grad, ctx.weight, dqkv, x2d, ctx.x_shape,
+                                pending=_take(ctx.link, "o_job"), sink=lambda jobs: _carry_or_launch(ctx.carry, jobs))
         return dx, dw, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1217,19 +1205,17 @@ _ROPE_ATTN_FUSED = True  # (a test seam: tests/test_model_gpu.py compares agains
 
 
 def qkv_rope_attention(x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True,
-                       delta_box=None):
+                       link=None):
     """flash_attention(linear_rope(x, W_qkv, cos, sin)) — one fused autograd node when the HIP paths apply
-    (the two separate nodes otherwise). delta_box: see flash_attention."""
+    (the two separate nodes otherwise). link: see flash_attention."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     x2d = x.reshape(-1, x.shape[-1])
-    if (_ROPE_ATTN_FUSED and _TN_MODE in ("1", "rope") and head_dim == 128 and _tn_ok(x2d, weight)
-            and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-            and cos.shape == (x2d.shape[0], 64)):
+    if (_ROPE_ATTN_FUSED and _TN_MODE in ("1", "rope") and _tn_ok(x2d, weight)
+            and _rope_epilogue_ok(x2d, weight, cos, sin, head_dim)):
         return QKVRopeAttnFn.apply(x, weight, cos, sin, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim,
-                                   float(scale), bool(causal), delta_box,
-                                   _carry_take() if delta_box is not None else None)
+                                   float(scale), bool(causal), link, _carry_take() if link is not None else None)
     qkv = linear_rope(x, weight, cos, sin, n_q, n_kv, head_dim)
-    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, delta_box)
+    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link)
 
 
 # ----------------------------------------------------------------------------- LM head + CE
@@ -1695,29 +1681,6 @@ class LoRAWideFn(Function):
         return (dx, None, None, None, None, None, None, *dAs, *dBs)
 
 
-class LoRAGateUpFn(Function):
-    """gu = the LoRA-widened gate_up GEMM (its SwiGLU is formed by the consumer, LoRASwiGLUDownFn, inside the down
-    projection's widening pass). (The persistent GEMM's SwiGLU epilogue writing gu and act measured slower than the
-    plain wide GEMM + the SwiGLU kernel: 688 vs ~665 us at 8192 x 22016, r4_run20.)"""
-
-    @staticmethod
-    def forward(ctx, x, wide, K, scaling, p, seed, meta, *ab):
-        X, acat, state = _lora_wide_prep(x, wide, K, scaling, p, seed, meta, ab)
-        gu = _lora_gemm(X, wide)
-        ctx.save_for_backward(X, acat)
-        ctx.wide, ctx.adapters, ctx.meta = wide, ab, state
-        return gu.view(*x.shape[:-1], gu.shape[-1])
-
-    @staticmethod
-    def backward(ctx, dgu):
-        X, acat = ctx.saved_tensors
-        dx, dAs, dBs = _lora_wide_bwd(X, acat, ctx.wide, ctx.adapters, ctx.meta, dgu.reshape(-1, dgu.shape[-1]),
-                                      ctx.needs_input_grad[0])
-        if dx is not None:
-            dx = dx.view(ctx.meta[-1])
-        return (dx, None, None, None, None, None, None, *dAs, *dBs)
-
-
 class LoRASwiGLUDownFn(Function):
     """y = the LoRA-widened down projection of silu(gate) * up: the widening pass reads gu and forms the activation on
     the fly (csrc/lora.hip lora_fwd swiglu: no SwiGLU kernel, no act tensor); the backward applies the SwiGLU backward
@@ -1767,7 +1730,10 @@ def lora_swiglu_mlp(h, w_gate_up, w_down, l_gate_up, l_down) -> torch.Tensor:
             and gu_args[0][0].shape[0] % 256 == 0 and (gu_args[0][0].shape[0] // 2) % 128 == 0
             and gu_args[0][0].shape[1] % 128 == 0):
         (a, ga_As, ga_Bs), (b, dn_As, dn_Bs) = gu_args, dn_args
-        gu = LoRAGateUpFn.apply(h, *a, *ga_As, *ga_Bs)
+        # (gu's SwiGLU is formed by the consumer inside the down projection's widening pass. The persistent GEMM's
+        # SwiGLU epilogue writing gu and act measured slower than the plain wide GEMM + the SwiGLU kernel: 688 vs
+        # ~665 us at 8192 x 22016, r4_run20.)
+        gu = LoRAWideFn.apply(h, *a, *ga_As, *ga_Bs)
         return LoRASwiGLUDownFn.apply(gu, *b, *dn_As, *dn_Bs)
     return lora_linear(swiglu(lora_linear(h, w_gate_up, l_gate_up)), w_down, l_down)
 
@@ -1782,7 +1748,7 @@ class LoRAQKVRopeAttnFn(Function):
     def forward(ctx, x, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, wide, K, scaling, p,
                 seed, meta, *ab):
         X, acat, state = _lora_wide_prep(x, wide, K, scaling, p, seed, meta, ab)
-        qkv = _ext.ops().gemm_tn_rope(X, wide, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg(X.shape[0], wide.shape[0], X.shape[1]))
+        qkv = _ext.ops().gemm_tn_rope(X, wide, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
         out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
         ctx.save_for_backward(X, acat, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.wide, ctx.adapters, ctx.meta = wide, ab, state
@@ -1810,10 +1776,8 @@ def lora_qkv_rope_attention(x, weight, lora, cos, sin, cu_seqlens, max_seqlen, n
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     args = _lora_wide_args(lora, weight)
     x2d = x.reshape(-1, x.shape[-1])
-    if (args is not None and _ROPE_ATTN_FUSED and head_dim == 128 and _ext.use_hip(x2d)
-            and x2d.shape[0] % 256 == 0 and args[0][0].shape[0] % 256 == 0 and args[0][0].shape[1] % 128 == 0
-            and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-            and cos.shape == (x2d.shape[0], 64)):
+    if (args is not None and _ROPE_ATTN_FUSED and args[0][0].shape[1] % 128 == 0
+            and _rope_epilogue_ok(x2d, args[0][0], cos, sin, head_dim)):
         a, As, Bs = args
         return LoRAQKVRopeAttnFn.apply(x, cos, sin, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim, float(scale),
                                        bool(causal), *a, *As, *Bs)

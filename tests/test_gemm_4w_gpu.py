@@ -298,7 +298,7 @@ def test_wgrad_pair_one_launch(N0, K0, N1, K1, T, accumulate):
 
 def test_wgrad_pair_refuses_a_leftover_in_the_first_problem():
     """The partial last round must fall in the second problem (its fixup); a pair whose leftover tiles would reach into
-    the first one is refused (ops.fused._pair_ok routes such pairs to two launches)."""
+    the first one is refused (ops.fused._plan_wgrad routes such pairs to two launches)."""
     dy0 = torch.randn(256, 22016, device=DEV, dtype=torch.bfloat16)
     x0 = torch.randn(256, 2048, device=DEV, dtype=torch.bfloat16)
     dy1 = torch.randn(256, 256, device=DEV, dtype=torch.bfloat16)

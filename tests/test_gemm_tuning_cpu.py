@@ -54,7 +54,8 @@ def test_weight_gradient_pair_planning():
     p0 = torch.nn.Parameter(torch.zeros(256, 256))
     p1 = torch.nn.Parameter(torch.zeros(256, 256))
     x = torch.zeros(1024, 256, dtype=torch.bfloat16)
-    assert not F._pair_ok(p0, x, x, p1, x, x)
+    assert F._job_tiles(p0, x, x) is None and F._job_tiles(p1, x, x) is None  # (no tile count: never grouped)
+    assert F._plan_wgrad([None, None], [1024, 1024]) == [F._Launch(0, 1), F._Launch(1, 1)]
 
 
 def test_dgrad_routing():
@@ -84,8 +85,9 @@ def test_dgrad_routing():
 
 def test_attention_wgrad_carry_into_the_previous_mlp_launch():
     """The cross-layer hand-off (ops.fused wgrad_carry_scope): the leftover split of a four-problem launch (1192
-    SmolLM3 tiles -> unsplit; Llama's 3328 tiles are whole rounds -> 1), a scope hands one MLP dict to the next
-    attention only, an armed dict takes the o_proj + qkv jobs and the MLP side then accumulates all four gradients
+    SmolLM3 tiles -> unsplit; Llama's 3328 tiles are whole rounds -> 1), a scope hands one MLP link to the next
+    attention only, a link whose gate_up backward runs takes the o_proj + qkv jobs and the MLP side then accumulates all
+    four gradients
     (CPU: the per-job fallback), and no carry outside a scope."""
     import torch
     import llm_fine_tune_distributed_amd.ops.fused as F
@@ -94,10 +96,11 @@ def test_attention_wgrad_carry_into_the_previous_mlp_launch():
     assert F._multi_split(1792 + 896 + 384 + 256, 8192) == 1
     assert F._carry_take() is None
     with F.wgrad_carry_scope(True):
-        box = {"armed": True}
-        F._carry_put(box)
-        assert F._carry_take() is box and F._carry_take() is None
-        F._carry_put({})  # an MLP whose gate_up backward will not run (unarmed) is never offered
+        link = F.MLPLink()
+        link.gate_up_runs = True
+        F._carry_put(link)
+        assert F._carry_take() is link and F._carry_take() is None
+        F._carry_put(F.MLPLink())  # an MLP whose gate_up backward will not run is never offered
         assert F._carry_take() is None
     assert F._CARRY is None
     torch.manual_seed(0)
@@ -110,10 +113,12 @@ def test_attention_wgrad_carry_into_the_previous_mlp_launch():
         return p, torch.randn(T, n), torch.randn(T, k)
 
     o, qkv, down, gu = job(8, 16), job(24, 16), job(16, 32), job(64, 16)
-    carry = {"armed": True}
+    carry = F.MLPLink()
+    carry.gate_up_runs = True
     F._carry_or_launch(carry, [o, qkv])
-    assert carry["attn"] == [o, qkv] and o[0].main_grad.abs().sum() == 0  # deferred, nothing computed yet
-    F._accumulate_weight_grad_jobs([down, gu] + carry.pop("attn"))
+    assert carry.attn_jobs == [o, qkv] and o[0].main_grad.abs().sum() == 0  # deferred, nothing computed yet
+    F._accumulate_weight_grad_jobs([down, gu] + F._take(carry, "attn_jobs"))
+    assert carry.attn_jobs is None
     for p, dy, x in (o, qkv, down, gu):
         assert torch.allclose(p.main_grad, dy.t() @ x, atol=1e-4)
     F._carry_or_launch(None, [o, qkv])  # no carry: launched at once (accumulating now)

@@ -60,7 +60,7 @@ def test_model_fused_gemm_epilogues(mt, down_fused, monkeypatch):
     labels[:, 200:] = -100
     calls = {"swiglu": 0, "rope": 0}
     # down_fused: gate_up GEMM + SwiGLU epilogue feeding the down GEMM whose dgrad carries the SwiGLU backward
-    # (GateUpActFn + SwiGLUDownFn); else GateUpSwiGLUFn + a plain down projection
+    # (GateUpActFn + SwiGLULinearFn given act); else GateUpSwiGLUFn + a plain down projection
     sw_fn = F.GateUpActFn if down_fused else F.GateUpSwiGLUFn
     monkeypatch.setattr(F, "_SWIGLU_DOWN", down_fused)
     orig_sw, orig_rope, orig_ra = sw_fn.apply, F.QKVRopeFn.apply, F.QKVRopeAttnFn.apply
