@@ -66,6 +66,10 @@ TORCH_LIBRARY(sftamd, m) {
   // q|k copy for the backward (empty with save_raw=False), bwd returns (dq_weight, dk_weight) in fp32
   m.def("qk_norm_rope_fwd(Tensor(a!) qkv, Tensor q_weight, Tensor k_weight, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim, float eps, bool save_raw=True) -> Tensor");
   m.def("qk_norm_rope_bwd(Tensor(a!) dqkv, Tensor qk_raw, Tensor q_weight, Tensor k_weight, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim, float eps) -> (Tensor, Tensor)");
+  // q / k / v projection bias + RoPE, in place on the packed qkv (csrc/qkv_bias.hip; Qwen2): fwd adds bias [(n_q + 2
+  // n_kv) * 128] and rotates the q|k columns; bwd un-rotates the q|k columns of dqkv and returns dbias in fp32
+  m.def("qkv_bias_rope_fwd(Tensor(a!) qkv, Tensor bias, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim) -> ()");
+  m.def("qkv_bias_rope_bwd(Tensor(a!) dqkv, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim) -> Tensor");
   m.def("embedding_fwd(Tensor ids, Tensor weight) -> Tensor");
   m.def("dropout_add(Tensor? a, Tensor b, float p, int seed) -> Tensor");
   m.def("lora_widen(Tensor x, int R, float p, int seed) -> (Tensor, Tensor)");

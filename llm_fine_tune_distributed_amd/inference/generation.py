@@ -36,11 +36,14 @@ class KVCache:
 def _rotate_qk_(at, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> None:
     """What a RoPE layer does to the q|k columns of the packed qkv between the projection and attention, in place:
     the rotation, behind the per-head RMSNorm for a qk-norm model (Qwen3; one kernel, and under no_grad it keeps no
-    copy for a backward). Shape-static for M = 1..B rows, so the graph decoders capture it."""
+    copy for a backward) or behind the q / k / v bias for a bias model (Qwen2; one kernel, which also adds the bias
+    to the v columns). Shape-static for M = 1..B rows, so the graph decoders capture it."""
     c = at.cfg
     nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
     if at.qk_norm:
         ops.qk_norm_rope_(qkv, at.q_norm.weight, at.k_norm.weight, cos, sin, nq, nkv, D, at.q_norm.eps)
+    elif at.has_qkv_bias:
+        ops.qkv_bias_rope_(qkv, at.qkv_bias, cos, sin, nq, nkv, D)
     else:
         ops.rope_(qkv, cos, sin, nq, nkv, D)
 

@@ -42,11 +42,16 @@ class ModelConfig:
     # RMSNorm over every query and key head after the projection, before RoPE (Qwen3: self_attn.q_norm / k_norm).
     # None: decided by the model type.
     qk_norm: Optional[bool] = None
+    # Learned bias on the q, k and v projections (not on o_proj), added before RoPE (Qwen2 / Qwen2.5:
+    # self_attn.{q,k,v}_proj.bias). None: decided by the model type.
+    qkv_bias: Optional[bool] = None
     extra: Dict[str, Any] = field(default_factory=dict)
 
     def __post_init__(self):
         if self.qk_norm is None:
             self.qk_norm = self.model_type == "qwen3"
+        if self.qkv_bias is None:
+            self.qkv_bias = self.model_type == "qwen2"
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
         if self.num_key_value_heads is None:
@@ -81,6 +86,8 @@ class ModelConfig:
         per_layer = h * self.qkv_size + self.q_size * h + 3 * h * i + 2 * h
         if self.qk_norm:
             per_layer += 2 * self.head_dim
+        if self.qkv_bias:
+            per_layer += self.qkv_size
         emb = v * h
         head = 0 if self.tie_word_embeddings else v * h
         return self.num_hidden_layers * per_layer + emb + head + h
@@ -101,7 +108,7 @@ class ModelConfig:
     # ------------------------------------------------------------------ (de)serialisation
     def to_hf_dict(self) -> Dict[str, Any]:
         arch = {"smollm3": "SmolLM3ForCausalLM", "llama": "LlamaForCausalLM",
-                "qwen3": "Qwen3ForCausalLM"}.get(self.model_type, "LlamaForCausalLM")
+                "qwen3": "Qwen3ForCausalLM", "qwen2": "Qwen2ForCausalLM"}.get(self.model_type, "LlamaForCausalLM")
         d = {
             "architectures": [arch],
             "model_type": self.model_type,
@@ -132,6 +139,9 @@ class ModelConfig:
         if self.model_type == "qwen3":
             del d["mlp_bias"]  # not a Qwen3Config key
             d["use_sliding_window"] = False
+        if self.model_type == "qwen2":
+            del d["mlp_bias"], d["attention_bias"]  # not Qwen2Config keys: the q / k / v biases are unconditional
+            d["use_sliding_window"] = False
         d.update(self.extra)
         return d
 
@@ -149,17 +159,23 @@ class ModelConfig:
         if isinstance(kw.get("eos_token_id"), list):
             kw["eos_token_id"] = kw["eos_token_id"][0]
         kw.setdefault("model_type", d.get("model_type", "llama"))
-        if kw["model_type"] not in ("smollm3", "llama", "qwen3"):
+        if kw["model_type"] not in ("smollm3", "llama", "qwen3", "qwen2"):
             kw["model_type"] = "llama"
-        if kw["model_type"] == "qwen3":
-            # what a Qwen3 config may ask for and this model does not implement: fail here, not in the weights loader
-            if d.get("attention_bias"):
+        mt = kw["model_type"]
+        if mt in ("qwen3", "qwen2"):
+            # what a Qwen config may ask for and this model does not implement: fail here, not in the weights loader
+            if mt == "qwen3" and d.get("attention_bias"):
                 raise NotImplementedError("qwen3: attention_bias=true is not supported (the projections have no bias)")
             if d.get("use_sliding_window"):
-                raise NotImplementedError("qwen3: use_sliding_window=true is not supported (full attention only)")
+                raise NotImplementedError(f"{mt}: use_sliding_window=true is not supported (full attention only)")
             bad = sorted({t for t in (d.get("layer_types") or []) if t != "full_attention"})
             if bad:
-                raise NotImplementedError(f"qwen3: layer_types {bad} are not supported (full_attention only)")
+                raise NotImplementedError(f"{mt}: layer_types {bad} are not supported (full_attention only)")
+        if mt == "qwen2":
+            # inert with use_sliding_window=false; kept so that a saved config says what the checkpoint's said
+            extra = {k: d[k] for k in ("sliding_window", "max_window_layers") if k in d}
+            if extra:
+                kw["extra"] = extra
         return cls(**kw)
 
     @classmethod
@@ -209,6 +225,33 @@ def qwen3_8b() -> ModelConfig:
     return _qwen3(hidden_size=4096, intermediate_size=12288, tie_word_embeddings=False)
 
 
+# The Qwen2.5 shapes below are written from memory of the published config.json files too (no copy of them was at
+# hand): a real checkpoint directory's own config.json always wins (get_config on the directory).
+def _qwen2_5(**kw) -> ModelConfig:
+    base = dict(model_type="qwen2", vocab_size=151936, head_dim=128, rope_theta=1_000_000.0, rms_norm_eps=1e-6,
+                max_position_embeddings=32768, bos_token_id=151643, eos_token_id=151645, pad_token_id=None)
+    base.update(kw)
+    return ModelConfig(**base)
+
+
+def qwen2_5_1_5b() -> ModelConfig:
+    """Qwen/Qwen2.5-1.5B-Instruct shape (12 q / 2 kv heads, tied embeddings)."""
+    return _qwen2_5(hidden_size=1536, intermediate_size=8960, num_hidden_layers=28, num_attention_heads=12,
+                    num_key_value_heads=2, tie_word_embeddings=True)
+
+
+def qwen2_5_3b() -> ModelConfig:
+    """Qwen/Qwen2.5-3B-Instruct shape (16 q / 2 kv heads, tied embeddings)."""
+    return _qwen2_5(hidden_size=2048, intermediate_size=11008, num_hidden_layers=36, num_attention_heads=16,
+                    num_key_value_heads=2, tie_word_embeddings=True)
+
+
+def qwen2_5_7b() -> ModelConfig:
+    """Qwen/Qwen2.5-7B-Instruct shape (28 q / 4 kv heads, untied lm_head, vocabulary padded to 152064)."""
+    return _qwen2_5(hidden_size=3584, intermediate_size=18944, num_hidden_layers=28, num_attention_heads=28,
+                    num_key_value_heads=4, vocab_size=152064, tie_word_embeddings=False)
+
+
 def tiny(model_type: str = "smollm3", **kw) -> ModelConfig:
     """Small config with the same structure (GQA, NoPE interval, tied head) for tests."""
     base = dict(
@@ -237,6 +280,15 @@ PRESETS = {
     "Qwen/Qwen3-8B": qwen3_8b,
     "tiny-qwen3": lambda: tiny("qwen3"),
     "tiny-gpu-qwen3": lambda: tiny("qwen3", hidden_size=256, num_attention_heads=2, num_key_value_heads=1,
+                                   head_dim=128, intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
+    "qwen2.5-1.5b": qwen2_5_1_5b,
+    "Qwen/Qwen2.5-1.5B": qwen2_5_1_5b,
+    "qwen2.5-3b": qwen2_5_3b,
+    "Qwen/Qwen2.5-3B": qwen2_5_3b,
+    "qwen2.5-7b": qwen2_5_7b,
+    "Qwen/Qwen2.5-7B": qwen2_5_7b,
+    "tiny-qwen2": lambda: tiny("qwen2"),
+    "tiny-gpu-qwen2": lambda: tiny("qwen2", hidden_size=256, num_attention_heads=2, num_key_value_heads=1,
                                    head_dim=128, intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
 }
 

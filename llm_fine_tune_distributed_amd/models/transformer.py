@@ -1,4 +1,4 @@
-"""Decoder-only causal LM (SmolLM3 / Llama / Qwen3 families) built on the fused ops.
+"""Decoder-only causal LM (SmolLM3 / Llama / Qwen3 / Qwen2 families) built on the fused ops.
 
 Replaces ``AutoModelForCausalLM.from_pretrained(...)`` of the reference
 (``training.py:97-105``) and the transformers modules it runs
@@ -57,14 +57,18 @@ class Attention(nn.Module):
         if self.qk_norm:  # Qwen3: RMSNorm over each query / key head (one weight [head_dim] per layer), before RoPE
             self.q_norm = RMSNorm(cfg.head_dim, cfg.rms_norm_eps)
             self.k_norm = RMSNorm(cfg.head_dim, cfg.rms_norm_eps)
+        self.has_qkv_bias = bool(cfg.qkv_bias)
+        assert not (self.qk_norm and self.has_qkv_bias), "qk_norm and qkv_bias are not implemented together"
+        if self.has_qkv_bias:  # Qwen2: q_proj / k_proj / v_proj biases as one vector in the fused weight's row order
+            self.qkv_bias = nn.Parameter(torch.zeros(cfg.qkv_size))
         self.lora = None  # set by apply_lora
         self.cp_group = None  # context-parallel process group (CausalLM.enable_context_parallel)
         self.cp_layout = "zigzag"
 
     def forward(self, h, rope_cs, cu_seqlens, max_seqlen):
         c = self.cfg
-        if self.qk_norm:
-            return self._forward_qk_norm(h, rope_cs, cu_seqlens, max_seqlen)
+        if self.qk_norm or self.has_qkv_bias:
+            return self._forward_mid_node(h, rope_cs, cu_seqlens, max_seqlen)
         if self.lora is None and self.use_rope and self.cp_group is None:
             # projection + RoPE (GEMM epilogue) + attention as one autograd node: the backward applies the inverse
             # rotation inside the attention kernels' dq / dK epilogues
@@ -104,21 +108,25 @@ class Attention(nn.Module):
                 return ops.attn_out_linear(a, self.o_proj, link)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
 
-    def _forward_qk_norm(self, h, rope_cs, cu_seqlens, max_seqlen):
-        """A qk-norm layer (Qwen3): projection, then the per-head norm + RoPE in place on the GEMM output, then
-        attention. The norm sits between the GEMM and the rotation, so the fused qkv + RoPE epilogue does not apply:
-        this is the NoPE layer's composition (o_proj + qkv weight gradients as one launch, carried into the previous
-        MLP's; the attention delta from the o_proj dgrad epilogue) with the new node in the middle. The projection
-        node saves its input, not its output, so the in-place node modifies nothing another node has saved."""
+    def _forward_mid_node(self, h, rope_cs, cu_seqlens, max_seqlen):
+        """A layer with a node between the projection and the rotation: the per-head norm of a qk-norm layer (Qwen3:
+        ops.qk_norm_rope_) or the q / k / v bias of a bias layer (Qwen2: ops.qkv_bias_rope_), each fused with RoPE and
+        in place on the GEMM output, then attention. The fused qkv + RoPE epilogue does not apply: this is the NoPE
+        layer's composition (o_proj + qkv weight gradients as one launch, carried into the previous MLP's; the
+        attention delta from the o_proj dgrad epilogue) with the node in the middle. The projection node saves its
+        input, not its output, so the in-place node modifies nothing another node has saved."""
         c = self.cfg
         nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-        assert self.use_rope, "qk-norm layers rotate on every layer"
+        assert self.use_rope, "qk-norm and qkv-bias layers rotate on every layer"
         plain = self.lora is None and self.cp_group is None
         link = ops.AttnLink() if plain else None
         qkv = (ops.qkv_in_linear(h, self.qkv_proj, link) if self.lora is None
                else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
-        qkv = ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, rope_cs[0], rope_cs[1], nq, nkv, D,
-                                self.q_norm.eps)
+        if self.qk_norm:
+            qkv = ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, rope_cs[0], rope_cs[1], nq, nkv, D,
+                                    self.q_norm.eps)
+        else:
+            qkv = ops.qkv_bias_rope_(qkv, self.qkv_bias, rope_cs[0], rope_cs[1], nq, nkv, D)
         if self.cp_group is not None:
             from ..parallel.context_parallel import ring_attention
             a = ring_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, self.cp_group, layout=self.cp_layout)
@@ -186,7 +194,7 @@ class Model(nn.Module):
 
 
 class CausalLM(nn.Module):
-    """SmolLM3ForCausalLM / LlamaForCausalLM / Qwen3ForCausalLM equivalent."""
+    """SmolLM3ForCausalLM / LlamaForCausalLM / Qwen3ForCausalLM / Qwen2ForCausalLM equivalent."""
 
     def __init__(self, cfg: ModelConfig):
         super().__init__()
@@ -240,6 +248,8 @@ class CausalLM(nn.Module):
         for name, p in self.named_parameters():
             if name.endswith("layernorm.weight") or name.endswith("norm.weight"):
                 p.fill_(1.0)
+            elif name.endswith("qkv_bias"):
+                p.zero_()  # as in HF
             elif p.device.type == "cpu":
                 p.copy_(torch.randn(p.shape, generator=g, dtype=torch.float32).mul_(std).to(p.dtype))
             else:
@@ -363,6 +373,11 @@ class CausalLM(nn.Module):
             if l.self_attn.qk_norm:
                 sd[p + "self_attn.q_norm.weight"] = l.self_attn.q_norm.weight.detach()
                 sd[p + "self_attn.k_norm.weight"] = l.self_attn.k_norm.weight.detach()
+            if l.self_attn.has_qkv_bias:
+                bq, bk, bv = l.self_attn.qkv_bias.detach().split([cfg.q_size, cfg.kv_size, cfg.kv_size], 0)
+                sd[p + "self_attn.q_proj.bias"] = bq
+                sd[p + "self_attn.k_proj.bias"] = bk
+                sd[p + "self_attn.v_proj.bias"] = bv
             g, u = l.mlp.gate_up_proj.detach().split([cfg.intermediate_size] * 2, 0)
             sd[p + "mlp.gate_proj.weight"] = g
             sd[p + "mlp.up_proj.weight"] = u
@@ -393,6 +408,10 @@ class CausalLM(nn.Module):
             if l.self_attn.qk_norm:
                 l.self_attn.q_norm.weight.copy_(take(p + "self_attn.q_norm.weight"))
                 l.self_attn.k_norm.weight.copy_(take(p + "self_attn.k_norm.weight"))
+            if l.self_attn.has_qkv_bias:
+                l.self_attn.qkv_bias.copy_(torch.cat([take(p + "self_attn.q_proj.bias"),
+                                                      take(p + "self_attn.k_proj.bias"),
+                                                      take(p + "self_attn.v_proj.bias")], 0))
             l.mlp.gate_up_proj.copy_(torch.cat([take(p + "mlp.gate_proj.weight"), take(p + "mlp.up_proj.weight")], 0))
             l.mlp.down_proj.copy_(take(p + "mlp.down_proj.weight"))
             l.input_layernorm.weight.copy_(take(p + "input_layernorm.weight"))

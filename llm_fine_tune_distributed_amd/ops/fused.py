@@ -1122,6 +1122,64 @@ def qk_norm_rope_(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps):
     return QKNormRopeFn.apply(qkv, q_weight, k_weight, cos, sin, n_q, n_kv, head_dim, eps)
 
 
+# ----------------------------------------------------------------------------- qkv bias + RoPE (in place, Qwen2)
+def _qkv_bias_hip(qkv: torch.Tensor, head_dim: int) -> bool:
+    """The HIP kernels (csrc/qkv_bias.hip) are built for head_dim 128 (every Qwen2.5 size from 1.5B up); other head
+    sizes take the reference. What the op cannot take at head_dim 128 (dtype, layout) fails its checks."""
+    return _ext.use_hip(qkv) and head_dim == 128
+
+
+def _qkv_bias_rope_fwd_inplace(qkv, bias, cos, sin, n_q, n_kv, hd):
+    if _qkv_bias_hip(qkv, hd):
+        _ext.ops().qkv_bias_rope_fwd(qkv, bias, cos, sin, n_q, n_kv, hd)
+    else:
+        qkv.copy_(ref.qkv_bias_rope(qkv, bias, cos, sin, n_q, n_kv, hd))
+
+
+class QKVBiasRopeFn(Function):
+    """In place on the packed qkv [M, (n_q + 2 n_kv) * D]: every q / k head row <- rope(row + bias), every v head row
+    <- row + bias (ops.reference.qkv_bias_rope). The node is linear: nothing is saved but the RoPE tables. The backward
+    un-rotates the incoming gradient in place and returns it; dbias is its column sums, computed only when the bias
+    takes a gradient (a frozen bias costs the plain inverse RoPE kernel)."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, cos, sin, n_q, n_kv, head_dim):
+        _qkv_bias_rope_fwd_inplace(qkv, bias, cos, sin, n_q, n_kv, head_dim)
+        ctx.save_for_backward(cos, sin)
+        ctx.bias = bias
+        ctx.dims = (n_q, n_kv, head_dim)
+        ctx.mark_dirty(qkv)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        cos, sin = ctx.saved_tensors
+        n_q, n_kv, hd = ctx.dims
+        dqkv = dqkv.contiguous()
+        if not ctx.needs_input_grad[1]:
+            _rope_inplace(dqkv, cos, sin, n_q, n_kv, hd, inverse=True)
+            return dqkv, None, None, None, None, None, None
+        if _qkv_bias_hip(dqkv, hd):
+            dbias = _ext.ops().qkv_bias_rope_bwd(dqkv, cos, sin, n_q, n_kv, hd)
+        else:
+            M, w = dqkv.shape[0], (n_q + n_kv) * hd
+            ct = torch.float64 if dqkv.dtype == torch.float64 else torch.float32
+            g = ref.apply_rope(dqkv[:, :w].to(ct).view(M, n_q + n_kv, hd), cos.to(ct), sin.to(ct), inverse=True)
+            g = g.reshape(M, w)
+            dbias = torch.cat([g.sum(0), dqkv[:, w:].to(ct).sum(0)])
+            dqkv[:, :w].copy_(g)
+        return dqkv, _accumulate_small_grad(ctx.bias, dbias), None, None, None, None, None
+
+
+def qkv_bias_rope_(qkv, bias, cos, sin, n_q, n_kv, head_dim):
+    """q / k / v projection bias + RoPE in place on the packed qkv (returns qkv). With nothing to differentiate
+    (torch.no_grad(): generation) no autograd node is made: the call is one kernel and can be captured into a graph."""
+    if not (torch.is_grad_enabled() and (qkv.requires_grad or bias.requires_grad)):
+        _qkv_bias_rope_fwd_inplace(qkv, bias, cos, sin, n_q, n_kv, head_dim)
+        return qkv
+    return QKVBiasRopeFn.apply(qkv, bias, cos, sin, n_q, n_kv, head_dim)
+
+
 # ----------------------------------------------------------------------------- attention
 class FlashAttnFn(Function):
     @staticmethod

@@ -103,6 +103,19 @@ def qk_norm_rope_bwd(dqkv: torch.Tensor, qk_raw: torch.Tensor, qw: torch.Tensor,
     return (dx.reshape(M, nh * D).to(dqkv.dtype), gx[:, :n_q].sum((0, 1)), gx[:, n_q:].sum((0, 1)))
 
 
+def qkv_bias_rope(qkv: torch.Tensor, bias: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_q: int, n_kv: int,
+                  head_dim: int) -> torch.Tensor:
+    """q / k / v projection bias + RoPE on the packed qkv [M, (n_q + 2 n_kv) * D] (Qwen2): every q and k head row
+    becomes rope(row + bias[head cols]), every v head row becomes row + bias[head cols]; bias [(n_q + 2 n_kv) * D].
+    Math in fp32 (fp64 for fp64 inputs), one rounding to the input dtype. Out of place and differentiable by autograd
+    in qkv and bias."""
+    M, nh, D = qkv.shape[0], n_q + n_kv, head_dim
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    x = qkv.to(ct) + bias.to(ct)[None]
+    y = apply_rope(x[:, : nh * D].view(M, nh, D), cos.to(ct), sin.to(ct))
+    return torch.cat([y.reshape(M, nh * D), x[:, nh * D:]], dim=-1).to(qkv.dtype)
+
+
 def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens: torch.Tensor,
               scale: Optional[float] = None, causal: bool = True) -> torch.Tensor:
     """Varlen causal GQA attention on the packed qkv layout [M, (n_q+2n_kv)*D] -> [M, n_q*D]."""
