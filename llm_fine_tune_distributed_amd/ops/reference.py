@@ -118,8 +118,10 @@ def qkv_bias_rope(qkv: torch.Tensor, bias: torch.Tensor, cos: torch.Tensor, sin:
 
 def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens: torch.Tensor,
               scale: Optional[float] = None, causal: bool = True) -> torch.Tensor:
-    """Varlen causal GQA attention on the packed qkv layout [M, (n_q+2n_kv)*D] -> [M, n_q*D]."""
+    """Varlen causal GQA attention on the packed qkv layout [M, (n_q+2n_kv)*D] -> [M, n_q*D]. Math in fp32 (fp64 for
+    fp64 inputs: the tests' reference), one rounding to the input dtype."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
     M = qkv.shape[0]
     q = qkv[:, : n_q * head_dim].view(M, n_q, head_dim)
     k = qkv[:, n_q * head_dim: (n_q + n_kv) * head_dim].view(M, n_kv, head_dim)
@@ -131,9 +133,9 @@ def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens:
         s, e = cu[i], cu[i + 1]
         if e <= s:
             continue
-        qi = q[s:e].float().transpose(0, 1)  # [H, T, D]
-        ki = k[s:e].float().transpose(0, 1).repeat_interleave(rep, 0)
-        vi = v[s:e].float().transpose(0, 1).repeat_interleave(rep, 0)
+        qi = q[s:e].to(ct).transpose(0, 1)  # [H, T, D]
+        ki = k[s:e].to(ct).transpose(0, 1).repeat_interleave(rep, 0)
+        vi = v[s:e].to(ct).transpose(0, 1).repeat_interleave(rep, 0)
         att = (qi @ ki.transpose(-1, -2)) * scale
         if causal:
             T = e - s

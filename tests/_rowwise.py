@@ -169,6 +169,27 @@ def decode_refs(q, K, V, scale):
     return run(torch.float64), run(torch.float32).to(BF16)
 
 
+# ------------------------------------------------------------------------------------------------ LoRA adapter gradients
+def lora_adapter_grad_refs(x, dy, As, Bs, meta, s, ct=torch.float64, rounding=False):
+    """(dAs, dBs) of the wide LoRA backward (ops.fused._lora_wide_bwd, dropout 0) for bf16 x [T, K], dy [T, n], adapters
+    A_i [r, K], B_i [rows_i, r] of the sub-projection at dy's columns [o_i, o_i + rows_i) (``meta`` [(o, rows, c)]) and
+    the scale s: dB_i = dy_i^T (s x A_i^T), dA_i = (s dy_i B_i)^T x. ``ct`` fp64 without rounding is the reference;
+    fp32 with ``rounding`` rounds where the kernels of csrc/lora.hip (and their torch twins on the shapes the kernels
+    do not take) round: the adapter columns s x A^T of the widened activation are bf16 (fwd_kernel's store, l. 205;
+    ops.reference.lora_fwd), dxa = s dy B is bf16 (dxa_kernel l. 719, dxa_finish_kernel l. 829; torch.addmm in bf16),
+    the two token reductions are fp32 sums of bf16 products (tsum_kernel) and each gradient is rounded once to the
+    parameter's bf16 (grad_out_kernel l. 472; ops.fused._accumulate_small_grad)."""
+    r = (lambda t: t.to(BF16).to(ct)) if rounding else (lambda t: t)
+    xc, dyc = x.to(ct), dy.to(ct)
+    dAs, dBs = [], []
+    for A, B, (o, rows, _) in zip(As, Bs, meta):
+        xa = r((xc @ A.to(ct).t()) * s)
+        dxa = r((dyc[:, o:o + rows] @ B.to(ct)) * s)
+        dBs.append(r(dyc[:, o:o + rows].t() @ xa))
+        dAs.append(r(dxa.t() @ xc))
+    return dAs, dBs
+
+
 # ------------------------------------------------------------------------------------------------ sampler twin
 SKIP_EPS = 1e-4  # ~30 x the fp32 error of a <= 64-term softmax with native exp at |x| <= 20
 
