@@ -14,6 +14,14 @@ top-k -> top-p -> multinomial.
 sequence (``BatchKVCache``), and a ``BatchGraphDecoder`` whose captured step runs B rows through
 the batched decode attention and the batched sampler, so the weights are read once per step for
 the whole batch. Element b of its result is what ``generate`` returns for prompt b with seed + b.
+
+Structure: the layer sequence is written once (``_run_layers``), the final norm + lm_head once (``_logits``). A path
+is the ``attend(li, qkv)`` it passes in, which stores the step's K/V and attends: ``forward_cached`` prefill (slice
+store, flash attention), ``forward_cached`` decode (slice store, eager fp32 attention: the CPU step),
+``GraphDecoder`` (``index_copy_`` at the device position, ``ops.decode_attention``), ``prefill_batch`` (scatter
+into the slabs, varlen flash attention) and ``BatchGraphDecoder`` (``ops.decode_attention_batched`` stores and
+attends). What a layer does to q|k before attention is ``Attention.rotate_qk_``, shared with training. ``_capture``
+turns a step into a hipGraph; the two sampler classes share ``_presence`` and ``_sampler_params``.
 """
 from __future__ import annotations
 
@@ -33,68 +41,76 @@ class KVCache:
         self.len = 0
 
 
-def _rotate_qk_(at, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> None:
-    """What a RoPE layer does to the q|k columns of the packed qkv between the projection and attention, in place:
-    the rotation, behind the per-head RMSNorm for a qk-norm model (Qwen3; one kernel, and under no_grad it keeps no
-    copy for a backward) or behind the q / k / v bias for a bias model (Qwen2; one kernel, which also adds the bias
-    to the v columns). Shape-static for M = 1..B rows, so the graph decoders capture it."""
-    c = at.cfg
-    nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-    if at.qk_norm:
-        ops.qk_norm_rope_(qkv, at.q_norm.weight, at.k_norm.weight, cos, sin, nq, nkv, D, at.q_norm.eps)
-    elif at.has_qkv_bias:
-        ops.qkv_bias_rope_(qkv, at.qkv_bias, cos, sin, nq, nkv, D)
-    else:
-        ops.rope_(qkv, cos, sin, nq, nkv, D)
+def _heads(cfg):
+    return cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+
+
+def _kv_rows(cfg, qkv: torch.Tensor):
+    """The k and v columns of the packed qkv [M, (nq + 2 nkv) D] as [M, nkv, D] views."""
+    nq, nkv, D = _heads(cfg)
+    M = qkv.shape[0]
+    return qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D), qkv[:, (nq + nkv) * D:].view(M, nkv, D)
 
 
 @torch.no_grad()
-def _layer(model, li, x, residual, cache: KVCache, pos: torch.Tensor, prefill: bool):
+def _run_layers(model, ids: torch.Tensor, pos: torch.Tensor, attend):
+    """Embeds ``ids`` [M] and runs every decoder layer on them at positions ``pos`` [M]: norm, qkv projection (plain
+    or LoRA), the layer's q|k op (Attention.rotate_qk_; the RoPE tables are built once per pass), attention, o
+    projection, norm, MLP. ``attend(li, qkv) -> a [M, nq * D]`` is the part the paths differ in: it stores the rows'
+    K/V of layer li in its cache and attends. Returns the last MLP output and the residual stream before adding it
+    (``_logits`` adds and norms them)."""
     cfg = model.config
-    layer = model.model.layers[li]
-    at = layer.self_attn
-    nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-    h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
-    qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
-    if at.use_rope:
-        cos, sin = model.rope_tables(pos)
-        _rotate_qk_(at, qkv, cos, sin)
-    M = qkv.shape[0]
-    k = qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D)
-    v = qkv[:, (nq + nkv) * D:].view(M, nkv, D)
-    s = cache.len
-    cache.k[li, s:s + M] = k
-    cache.v[li, s:s + M] = v
-    if prefill:
-        cu = torch.tensor([0, M], dtype=torch.int32, device=x.device)
-        a = ops.flash_attention(qkv.contiguous(), cu, M, nq, nkv, D)
-    else:
-        q = qkv[:, :nq * D].view(nq, D).float()
-        K = cache.k[li, :s + 1].float()  # [S, nkv, D]
-        V = cache.v[li, :s + 1].float()
-        rep = nq // nkv
-        qg = q.view(nkv, rep, D)
-        att = torch.einsum("grd,sgd->grs", qg, K) / math.sqrt(D)
-        p = att.softmax(-1)
-        a = torch.einsum("grs,sgd->grd", p, V).reshape(1, nq * D).to(x.dtype)
-    o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
-    h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
-    return layer.mlp(h), residual
+    x = ops.embedding(ids, model.model.embed_tokens)
+    residual = None
+    cos = sin = None
+    for li, layer in enumerate(model.model.layers):
+        at = layer.self_attn
+        h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
+        qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
+        if at.use_rope:
+            if cos is None:
+                cos, sin = model.rope_tables(pos)
+            qkv = at.rotate_qk_(qkv, cos, sin)
+        a = attend(li, qkv)
+        o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
+        h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
+        x = layer.mlp(h)
+    return x, residual
+
+
+@torch.no_grad()
+def _logits(model, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    """Final norm and lm_head over the given rows of a ``_run_layers`` result: fp32 logits [rows, V]."""
+    h, _ = ops.add_rms_norm(x, residual, model.model.norm.weight, model.config.rms_norm_eps)
+    return torch.nn.functional.linear(h, model.lm_head_weight).float()
 
 
 @torch.no_grad()
 def forward_cached(model, ids: torch.Tensor, cache: KVCache, prefill: bool) -> torch.Tensor:
     """ids: [M] tokens appended at positions cache.len ... Returns last-token logits [V] (fp32)."""
-    M = ids.numel()
-    pos = torch.arange(cache.len, cache.len + M, device=ids.device)
-    x = ops.embedding(ids, model.model.embed_tokens)
-    residual = None
-    for li in range(model.config.num_hidden_layers):
-        x, residual = _layer(model, li, x, residual, cache, pos, prefill)
+    nq, nkv, D = _heads(model.config)
+    M, s = ids.numel(), cache.len
+    cu = torch.tensor([0, M], dtype=torch.int32, device=ids.device) if prefill else None
+
+    def store(li, qkv):
+        cache.k[li, s:s + M], cache.v[li, s:s + M] = _kv_rows(model.config, qkv)
+
+    def attend_prefill(li, qkv):
+        store(li, qkv)
+        return ops.flash_attention(qkv.contiguous(), cu, M, nq, nkv, D)
+
+    def attend_decode(li, qkv):  # one row, eagerly in fp32 over the cache (the CPU path's decode step)
+        store(li, qkv)
+        q = qkv[:, :nq * D].view(nq, D).float()
+        K = cache.k[li, :s + 1].float()  # [S, nkv, D]
+        V = cache.v[li, :s + 1].float()
+        att = torch.einsum("grd,sgd->grs", q.view(nkv, nq // nkv, D), K) / math.sqrt(D)
+        return torch.einsum("grs,sgd->grd", att.softmax(-1), V).reshape(1, nq * D).to(qkv.dtype)
+
+    pos = torch.arange(s, s + M, device=ids.device)
+    x, residual = _run_layers(model, ids, pos, attend_prefill if prefill else attend_decode)
     cache.len += M
-    n = model.model.norm
-    h, _ = ops.add_rms_norm(x[-1:], residual[-1:], n.weight, model.config.rms_norm_eps)
-    return torch.nn.functional.linear(h, model.lm_head_weight).float()[0]
+    return _logits(model, x[-1:], residual[-1:])[0]
 
 
 def sample_next(logits: torch.Tensor, history: torch.Tensor, temperature: float = 0.6, top_k: int = 40,
@@ -121,6 +137,23 @@ def sample_next(logits: torch.Tensor, history: torch.Tensor, temperature: float 
     return int(torch.multinomial(p, 1, generator=generator))
 
 
+def _presence(vocab_size: int, histories, device) -> torch.Tensor:
+    """Token histories as presence bitmasks [B, ceil(V / 32)] (int32 words; bit t & 31 of word t >> 5 is token t)."""
+    import numpy as np
+    words = np.zeros((len(histories), (vocab_size + 31) // 32), dtype=np.uint32)
+    for b, hist in enumerate(histories):
+        ids = np.asarray(list(hist), dtype=np.int64)
+        np.bitwise_or.at(words[b], ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+    return torch.from_numpy(words.view(np.int32).copy()).to(device)
+
+
+def _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed):
+    """The scalar arguments of the two sampler ops, in their order. Greedy is top-1; no seed draws one."""
+    return (float(temperature), int(top_k) if do_sample else 1, float(top_p if top_p is not None else 1.0),
+            float(repetition_penalty or 1.0), bool(do_sample),
+            int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+
+
 class DeviceSampler:
     """GPU-resident sampling state of one sequence for the fused HIP sampler (csrc/sampler.hip): the
     history as a presence bitmask (repetition penalty is a set operation), a step counter that keys the
@@ -128,16 +161,10 @@ class DeviceSampler:
 
     def __init__(self, vocab_size: int, device, history_ids, max_new_tokens: int, seed: Optional[int],
                  temperature: float, top_k: int, top_p: Optional[float], repetition_penalty: float, do_sample: bool):
-        import numpy as np
-        words = np.zeros((vocab_size + 31) // 32, dtype=np.uint32)
-        ids = np.asarray(list(history_ids), dtype=np.int64)
-        np.bitwise_or.at(words, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
-        self.presence = torch.from_numpy(words.view(np.int32).copy()).to(device)
+        self.presence = _presence(vocab_size, [history_ids], device)[0]
         self.state = torch.zeros(4, dtype=torch.long, device=device)
         self.log = torch.full((max(1, max_new_tokens),), -1, dtype=torch.long, device=device)
-        self.params = (float(temperature), int(top_k) if do_sample else 1, float(top_p if top_p is not None else 1.0),
-                       float(repetition_penalty or 1.0), bool(do_sample),
-                       int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        self.params = _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed)
 
     @staticmethod
     def supported(top_k: int, do_sample: bool) -> bool:
@@ -154,6 +181,25 @@ def ops_ext():
     return _ext.ops()
 
 
+def _capture(body, live=()) -> "torch.cuda.CUDAGraph":
+    """``body`` as a hipGraph. It first runs twice on a side stream (allocator, kernel and library set-up outside
+    the capture); ``live`` are the tensors body advances (counters, sampler state), restored after the warm-up so
+    the real sequence state is untouched."""
+    saved = [t.clone() for t in live]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            body()
+    torch.cuda.current_stream().wait_stream(s)
+    for t, v in zip(live, saved):
+        t.copy_(v)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
+
+
 class GraphDecoder:
     """Static-shape decode step over a KVCache, captured once into a hipGraph (GPU)."""
 
@@ -166,57 +212,30 @@ class GraphDecoder:
         self.graph = None
         self.logits = None
 
-    @torch.no_grad()
+    def _attend(self, li: int, qkv: torch.Tensor) -> torch.Tensor:
+        nq, nkv, D = _heads(self.model.config)
+        k, v = _kv_rows(self.model.config, qkv)
+        self.cache.k[li].index_copy_(0, self.pos, k)
+        self.cache.v[li].index_copy_(0, self.pos, v)
+        return ops.decode_attention(qkv[0, :nq * D].contiguous(), self.cache.k[li], self.cache.v[li], self.len,
+                                    nq, nkv).view(1, nq * D)
+
     def _step(self) -> torch.Tensor:
-        m, cfg = self.model, self.model.config
-        nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        x = ops.embedding(self.tok, m.model.embed_tokens)
-        residual = None
-        cos = sin = None
-        for li, layer in enumerate(m.model.layers):
-            at = layer.self_attn
-            h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
-            qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
-            if at.use_rope:
-                if cos is None:
-                    cos, sin = m.rope_tables(self.pos)
-                _rotate_qk_(at, qkv, cos, sin)
-            self.cache.k[li].index_copy_(0, self.pos, qkv[:, nq * D:(nq + nkv) * D].view(1, nkv, D))
-            self.cache.v[li].index_copy_(0, self.pos, qkv[:, (nq + nkv) * D:].view(1, nkv, D))
-            a = ops.decode_attention(qkv[0, :nq * D].contiguous(), self.cache.k[li], self.cache.v[li], self.len,
-                                     nq, nkv).view(1, nq * D)
-            o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
-            h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
-            x = layer.mlp(h)
-        n = m.model.norm
-        h, _ = ops.add_rms_norm(x, residual, n.weight, cfg.rms_norm_eps)
-        return torch.nn.functional.linear(h, m.lm_head_weight).float()[0]
+        x, residual = _run_layers(self.model, self.tok, self.pos, self._attend)
+        return _logits(self.model, x, residual)[0]
 
     def run_sampled(self, sampler: DeviceSampler, n: int, use_graph: bool = True) -> None:
         """n decode steps entirely on the device: each step runs the model on self.tok at self.pos and the
         fused sampler writes the next token / position / KV length back into the step's inputs (one
         hipGraph holds both, so consecutive replays need no host involvement)."""
         def body():
-            logits = self._step()
-            sampler.sample(logits, self.tok, self.pos, self.len)
+            sampler.sample(self._step(), self.tok, self.pos, self.len)
         if not use_graph:
             for _ in range(n):
                 body()
             return
         if self.graph is None:
-            # warm up on copies of the counters so the real sequence state is untouched
-            saved = [t.clone() for t in (self.tok, self.pos, self.len, sampler.state, sampler.presence, sampler.log)]
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    body()
-            torch.cuda.current_stream().wait_stream(s)
-            for t, v in zip((self.tok, self.pos, self.len, sampler.state, sampler.presence, sampler.log), saved):
-                t.copy_(v)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                body()
+            self.graph = _capture(body, (self.tok, self.pos, self.len, sampler.state, sampler.presence, sampler.log))
         for _ in range(n):
             self.graph.replay()
 
@@ -227,15 +246,9 @@ class GraphDecoder:
         if not use_graph:
             return self._step()
         if self.graph is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):  # warm up allocator / kernels outside capture
-                    self._step()
-            torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            def body():  # the captured call's logits are the graph's static output
                 self.logits = self._step()
+            self.graph = _capture(body)
         self.graph.replay()
         return self.logits
 
@@ -319,9 +332,8 @@ class BatchKVCache:
 def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch.Tensor:
     """All prompts in ONE packed varlen pass (cu_seqlens, per-sample positions) through the ops forward_cached
     uses; K/V are scattered into each sequence's slab. Returns the last-token logits [B, V] (fp32)."""
-    cfg = model.config
     dev = model.model.embed_tokens.device
-    nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+    nq, nkv, D = _heads(model.config)
     n = [len(p) for p in prompts]
     assert len(n) == len(cache.lens) and min(n) > 0 and max(n) <= cache.k.shape[2], "prompts do not fit the cache"
     ids = torch.tensor([t for p in prompts for t in p], device=dev)
@@ -331,28 +343,15 @@ def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch
     cu = torch.tensor(bounds, dtype=torch.int32, device=dev)
     pos = torch.cat([torch.arange(x) for x in n]).to(dev)
     seq = torch.repeat_interleave(torch.arange(len(n)), torch.tensor(n)).to(dev)
-    M = ids.numel()
-    x = ops.embedding(ids, model.model.embed_tokens)
-    residual = None
-    cos = sin = None
-    for li, layer in enumerate(model.model.layers):
-        at = layer.self_attn
-        h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
-        qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
-        if at.use_rope:
-            if cos is None:
-                cos, sin = model.rope_tables(pos)
-            _rotate_qk_(at, qkv, cos, sin)
-        cache.k[li][seq, pos] = qkv[:, nq * D:(nq + nkv) * D].view(M, nkv, D)
-        cache.v[li][seq, pos] = qkv[:, (nq + nkv) * D:].view(M, nkv, D)
-        a = ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D)
-        o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
-        h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
-        x = layer.mlp(h)
+
+    def attend(li, qkv):
+        cache.k[li][seq, pos], cache.v[li][seq, pos] = _kv_rows(model.config, qkv)
+        return ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D)
+
+    x, residual = _run_layers(model, ids, pos, attend)
     cache.lens = list(n)
     last = (cu[1:] - 1).long()
-    h, _ = ops.add_rms_norm(x[last], residual[last], model.model.norm.weight, cfg.rms_norm_eps)
-    return torch.nn.functional.linear(h, model.lm_head_weight).float()
+    return _logits(model, x[last], residual[last])
 
 
 class BatchDeviceSampler:
@@ -363,20 +362,13 @@ class BatchDeviceSampler:
     def __init__(self, vocab_size: int, device, histories, max_new_tokens: int, seed: Optional[int],
                  eos_token_id: Optional[int], temperature: float, top_k: int, top_p: Optional[float],
                  repetition_penalty: float, do_sample: bool):
-        import numpy as np
         B = len(histories)
-        words = np.zeros((B, (vocab_size + 31) // 32), dtype=np.uint32)
-        for b, hist in enumerate(histories):
-            ids = np.asarray(list(hist), dtype=np.int64)
-            np.bitwise_or.at(words[b], ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
-        self.presence = torch.from_numpy(words.view(np.int32).copy()).to(device)
+        self.presence = _presence(vocab_size, histories, device)
         self.state = torch.zeros(B, 4, dtype=torch.long, device=device)
         self.log = torch.full((B, max(1, max_new_tokens)), -1, dtype=torch.long, device=device)
         self.done = torch.zeros(B, dtype=torch.int32, device=device)
         self.eos = -1 if eos_token_id is None else int(eos_token_id)
-        self.params = (float(temperature), int(top_k) if do_sample else 1, float(top_p if top_p is not None else 1.0),
-                       float(repetition_penalty or 1.0), bool(do_sample),
-                       int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        self.params = _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed)
 
     def sample(self, logits: torch.Tensor, tok_out=None, pos_out=None, len_out=None) -> None:
         t, k, p, rp, ds, seed = self.params
@@ -400,53 +392,24 @@ class BatchGraphDecoder:
         self.sampled_graph = None  # model step + sampler (run_sampled())
         self.logits = None
 
-    @torch.no_grad()
+    def _attend(self, li: int, qkv: torch.Tensor) -> torch.Tensor:  # the op appends each row's K/V itself
+        nq, nkv, _ = _heads(self.model.config)
+        return ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv)
+
     def _step(self) -> torch.Tensor:
-        m, cfg = self.model, self.model.config
-        nq, nkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        x = ops.embedding(self.tok, m.model.embed_tokens)
-        residual = None
-        cos = sin = None
-        for li, layer in enumerate(m.model.layers):
-            at = layer.self_attn
-            h, residual = ops.add_rms_norm(x, residual, layer.input_layernorm.weight, cfg.rms_norm_eps)
-            qkv = ops.linear(h, at.qkv_proj) if at.lora is None else ops.lora_linear(h, at.qkv_proj, at.lora["qkv"])
-            if at.use_rope:
-                if cos is None:
-                    cos, sin = m.rope_tables(self.pos)
-                _rotate_qk_(at, qkv, cos, sin)
-            a = ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv)
-            o = ops.linear(a, at.o_proj) if at.lora is None else ops.lora_linear(a, at.o_proj, at.lora["o"])
-            h, residual = ops.add_rms_norm(o, residual, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
-            x = layer.mlp(h)
-        n = m.model.norm
-        h, _ = ops.add_rms_norm(x, residual, n.weight, cfg.rms_norm_eps)
-        return torch.nn.functional.linear(h, m.lm_head_weight).float()
+        return _logits(self.model, *_run_layers(self.model, self.tok, self.pos, self._attend))
 
     def run_sampled(self, sampler: BatchDeviceSampler, n: int, use_graph: bool = True) -> None:
         """n decode steps of every row entirely on the device (model step + fused sampler in one hipGraph)."""
         def body():
-            logits = self._step()
-            sampler.sample(logits, self.tok, self.pos, self.len)
+            sampler.sample(self._step(), self.tok, self.pos, self.len)
         if not use_graph:
             for _ in range(n):
                 body()
             return
         if self.sampled_graph is None:
-            # warm up on copies of the counters so the real sequence state is untouched
-            live = (self.tok, self.pos, self.len, sampler.state, sampler.presence, sampler.log, sampler.done)
-            saved = [t.clone() for t in live]
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    body()
-            torch.cuda.current_stream().wait_stream(s)
-            for t, v in zip(live, saved):
-                t.copy_(v)
-            self.sampled_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.sampled_graph):
-                body()
+            self.sampled_graph = _capture(body, (self.tok, self.pos, self.len, sampler.state, sampler.presence,
+                                                 sampler.log, sampler.done))
         for _ in range(n):
             self.sampled_graph.replay()
 
@@ -464,15 +427,9 @@ class BatchGraphDecoder:
         if not use_graph:
             return self._step()
         if self.graph is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):  # warm up allocator / kernels outside capture
-                    self._step()
-            torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            def body():  # the captured call's logits are the graph's static output
                 self.logits = self._step()
+            self.graph = _capture(body)
         self.graph.replay()
         return self.logits
 

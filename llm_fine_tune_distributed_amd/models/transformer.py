@@ -65,75 +65,63 @@ class Attention(nn.Module):
         self.cp_group = None  # context-parallel process group (CausalLM.enable_context_parallel)
         self.cp_layout = "zigzag"
 
+    def rotate_qk_(self, qkv, cos, sin):
+        """What this layer does to the packed qkv between the projection and attention, in place; returns qkv.
+        Nothing on a NoPE layer. On a RoPE layer the rotation of the q|k columns: behind the per-head RMSNorm for a
+        qk-norm layer (Qwen3: ops.qk_norm_rope_), behind the q / k / v bias for a bias layer (Qwen2:
+        ops.qkv_bias_rope_, which also adds the bias to the v columns), each as one kernel. Under no_grad
+        (generation) the ops keep no copy for a backward and make no autograd node; they are shape-static, so the
+        graph decoders capture them."""
+        c = self.cfg
+        nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        if not self.use_rope:
+            return qkv
+        if self.qk_norm:
+            return ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, cos, sin, nq, nkv, D,
+                                     self.q_norm.eps)
+        if self.has_qkv_bias:
+            return ops.qkv_bias_rope_(qkv, self.qkv_bias, cos, sin, nq, nkv, D)
+        return ops.rope_(qkv, cos, sin, nq, nkv, D)
+
     def forward(self, h, rope_cs, cu_seqlens, max_seqlen):
         c = self.cfg
-        if self.qk_norm or self.has_qkv_bias:
-            return self._forward_mid_node(h, rope_cs, cu_seqlens, max_seqlen)
-        if self.lora is None and self.use_rope and self.cp_group is None:
-            # projection + RoPE (GEMM epilogue) + attention as one autograd node: the backward applies the inverse
-            # rotation inside the attention kernels' dq / dK epilogues
-            # the o_proj backward computes the attention backward's delta in its dgrad epilogue (link: the hand-off)
-            link = ops.AttnLink()
-            a = ops.qkv_rope_attention(h, self.qkv_proj, rope_cs[0], rope_cs[1], cu_seqlens, max_seqlen,
-                                       c.num_attention_heads, c.num_key_value_heads, c.head_dim, link=link)
-            return ops.attn_out_linear(a, self.o_proj, link)
-        if self.lora is not None and self.use_rope and self.cp_group is None:
+        nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        mid = self.qk_norm or self.has_qkv_bias  # a node between the projection and the rotation
+        assert self.use_rope or not mid, "qk-norm and qkv-bias layers rotate on every layer"
+        if self.use_rope and not mid and self.cp_group is None:
+            if self.lora is None:
+                # projection + RoPE (GEMM epilogue) + attention as one autograd node: the backward applies the
+                # inverse rotation inside the attention kernels' dq / dK epilogues
+                # the o_proj backward computes the attention backward's delta in its dgrad epilogue (link: the hand-off)
+                link = ops.AttnLink()
+                a = ops.qkv_rope_attention(h, self.qkv_proj, rope_cs[0], rope_cs[1], cu_seqlens, max_seqlen, nq, nkv, D,
+                                           link=link)
+                return ops.attn_out_linear(a, self.o_proj, link)
             # the LoRA-widened qkv GEMM with the RoPE epilogue + attention as one node (inverse RoPE in the backward's
             # dq / dK epilogues), the plain composition where the HIP path does not apply
             a = ops.lora_qkv_rope_attention(h, self.qkv_proj, self.lora["qkv"], rope_cs[0], rope_cs[1], cu_seqlens,
-                                            max_seqlen, c.num_attention_heads, c.num_key_value_heads, c.head_dim)
+                                            max_seqlen, nq, nkv, D)
             return ops.lora_linear(a, self.o_proj, self.lora["o"])
-        link = None
-        if self.lora is None and self.use_rope:
-            # projection + RoPE in one HIP GEMM (epilogue rotation) where the shapes allow
-            qkv = ops.linear_rope(h, self.qkv_proj, rope_cs[0], rope_cs[1], c.num_attention_heads,
-                                  c.num_key_value_heads, c.head_dim)
+        # The unfused composition: a NoPE layer, a layer with a mid node (the fused qkv + RoPE epilogue does not
+        # apply), a context-parallel layer. With a link (no LoRA, no context-parallel group) the qkv node also issues
+        # o_proj's weight gradient, as one launch with its own and carried into the previous MLP's, and the attention
+        # delta comes from the o_proj dgrad epilogue. The projection node saves its input, not its output, so the
+        # in-place rotate_qk_ modifies nothing another node has saved.
+        link = ops.AttnLink() if (self.lora is None and self.cp_group is None) else None
+        if self.lora is None and self.use_rope and not mid:
+            # (context parallel) projection + RoPE in one HIP GEMM (epilogue rotation) where the shapes allow
+            qkv = ops.linear_rope(h, self.qkv_proj, rope_cs[0], rope_cs[1], nq, nkv, D)
         else:
-            # (a NoPE layer: the qkv node also issues o_proj's weight gradient, as one launch with its own)
-            link = ops.AttnLink() if (self.lora is None and not self.use_rope and self.cp_group is None) else None
             qkv = (ops.qkv_in_linear(h, self.qkv_proj, link) if self.lora is None
                    else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
-            if self.use_rope:
-                qkv = ops.rope_(qkv, rope_cs[0], rope_cs[1], c.num_attention_heads, c.num_key_value_heads, c.head_dim)
-        if self.cp_group is not None:
-            from ..parallel.context_parallel import ring_attention
-            a = ring_attention(qkv, cu_seqlens, max_seqlen, c.num_attention_heads, c.num_key_value_heads, c.head_dim,
-                               self.cp_group, layout=self.cp_layout)
-        else:
-            if self.lora is None and link is None:
-                link = ops.AttnLink()
-            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, c.num_attention_heads, c.num_key_value_heads,
-                                    c.head_dim, link=link)
-            if link is not None:
-                return ops.attn_out_linear(a, self.o_proj, link)
-        return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
-
-    def _forward_mid_node(self, h, rope_cs, cu_seqlens, max_seqlen):
-        """A layer with a node between the projection and the rotation: the per-head norm of a qk-norm layer (Qwen3:
-        ops.qk_norm_rope_) or the q / k / v bias of a bias layer (Qwen2: ops.qkv_bias_rope_), each fused with RoPE and
-        in place on the GEMM output, then attention. The fused qkv + RoPE epilogue does not apply: this is the NoPE
-        layer's composition (o_proj + qkv weight gradients as one launch, carried into the previous MLP's; the
-        attention delta from the o_proj dgrad epilogue) with the node in the middle. The projection node saves its
-        input, not its output, so the in-place node modifies nothing another node has saved."""
-        c = self.cfg
-        nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-        assert self.use_rope, "qk-norm and qkv-bias layers rotate on every layer"
-        plain = self.lora is None and self.cp_group is None
-        link = ops.AttnLink() if plain else None
-        qkv = (ops.qkv_in_linear(h, self.qkv_proj, link) if self.lora is None
-               else ops.lora_linear(h, self.qkv_proj, self.lora["qkv"]))
-        if self.qk_norm:
-            qkv = ops.qk_norm_rope_(qkv, self.q_norm.weight, self.k_norm.weight, rope_cs[0], rope_cs[1], nq, nkv, D,
-                                    self.q_norm.eps)
-        else:
-            qkv = ops.qkv_bias_rope_(qkv, self.qkv_bias, rope_cs[0], rope_cs[1], nq, nkv, D)
+            qkv = self.rotate_qk_(qkv, rope_cs[0], rope_cs[1])
         if self.cp_group is not None:
             from ..parallel.context_parallel import ring_attention
             a = ring_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, self.cp_group, layout=self.cp_layout)
         else:
             a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, link=link)
-            if link is not None:
-                return ops.attn_out_linear(a, self.o_proj, link)
+        if link is not None:
+            return ops.attn_out_linear(a, self.o_proj, link)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
 
 
