@@ -538,7 +538,7 @@ std::tuple<at::Tensor, at::Tensor> lora_fwd(const at::Tensor& x, const at::Tenso
   const long T = x.size(0);
   SFT_CHECK(!swiglu || (x.size(1) % 2 == 0 && !save_xd), "lora_fwd swiglu: gu [T, 2K], no saved dropout(x)");
   const int K = swiglu ? x.size(1) / 2 : x.size(1), R = A.size(0);
-  SFT_CHECK(A.size(1) == K && K % 256 == 0 && R % 16 == 0 && R >= 16 && R <= 64, "lora_fwd: shapes");
+  SFT_CHECK(A.size(1) == K && K > 0 && K % 256 == 0 && R % 16 == 0 && R >= 16 && R <= 64, "lora_fwd: shapes");
   if (ldX <= 0) ldX = K + R;
   SFT_CHECK(ldX >= K + R && ldX % 8 == 0, "lora_fwd: ldX >= K + R, multiple of 8");
   auto X = at::empty({T, ldX}, x.options());
@@ -560,7 +560,8 @@ void lora_fwd_inplace(at::Tensor X, int64_t K, const at::Tensor& A, double s, do
             "lora_fwd_inplace: X [T, ldX] row-contiguous");
   const long T = X.size(0), ldX = X.size(1);
   const int R = A.size(0);
-  SFT_CHECK(A.size(1) == K && K % 256 == 0 && R % 16 == 0 && R >= 16 && R <= 64 && ldX >= K + R && ldX % 8 == 0,
+  SFT_CHECK(A.size(1) == K && K > 0 && K % 256 == 0 && R % 16 == 0 && R >= 16 && R <= 64 && ldX >= K + R &&
+                ldX % 8 == 0,
             "lora_fwd_inplace: shapes");
   if (T == 0) return;
   lora::launch_fwd((const u16*)X.data_ptr(), ldX, 0, A, (u16*)X.data_ptr(), nullptr, T, (int)K, ldX, s, p, seed,
@@ -579,8 +580,10 @@ at::Tensor lora_bwd_dx(const at::Tensor& base, const at::Tensor& dxa, const at::
   SFT_CHECK_CONTIG(A);
   const long T = base.size(0);
   const int K = base.size(1), R = A.size(0);
-  SFT_CHECK(base.stride(1) == 1 && base.stride(0) % 8 == 0 && K % 8 == 0, "lora_bwd_dx: base layout");
-  SFT_CHECK(dxa.size(0) == T && dxa.size(1) == R && A.size(1) == K && R % 16 == 0 && R <= 64, "lora_bwd_dx: shapes");
+  SFT_CHECK(base.stride(1) == 1 && base.stride(0) % 8 == 0 && (uintptr_t)base.data_ptr() % 16 == 0 && K > 0 &&
+                K % 8 == 0, "lora_bwd_dx: base rows 16-byte aligned");
+  SFT_CHECK(dxa.size(0) == T && dxa.size(1) == R && A.size(1) == K && R % 16 == 0 && R >= 16 && R <= 64,
+            "lora_bwd_dx: shapes");
   const bool sw = gu.has_value() && gu->defined();
   if (sw) {
     SFT_CHECK_BF16(*gu);
@@ -937,7 +940,8 @@ at::Tensor lora_tsum(const at::Tensor& X, int64_t K, const at::Tensor& S, double
   SFT_CHECK_BF16(S);
   const long T = X.size(0);
   const int R = S.size(1);
-  SFT_CHECK(X.stride(1) == 1 && X.stride(0) % 8 == 0 && X.size(1) >= K && K % 8 == 0, "lora_tsum: X layout");
+  SFT_CHECK(X.stride(1) == 1 && X.stride(0) % 8 == 0 && (uintptr_t)X.data_ptr() % 16 == 0 && X.size(1) >= K && K > 0 &&
+                K % 8 == 0, "lora_tsum: X layout");
   SFT_CHECK(S.stride(1) == 1 && S.stride(0) % 8 == 0 && (uintptr_t)S.data_ptr() % 16 == 0, "lora_tsum: S layout");
   SFT_CHECK(S.size(0) == T && R % 16 == 0 && R >= 16 && R <= 64, "lora_tsum: S [T, R], R in 16..64");
   if (T == 0) return at::zeros({1, R, K}, X.options().dtype(at::kFloat));
