@@ -22,6 +22,8 @@
 //   p(8g+j) = j<4 ? 4g+j : 16+4g+(j-4) on BOTH operands of the next MFMA.
 // The 32x32x16 lane maps are at fwd32 below.
 #include "common.h"
+#include "gemm_prims.h"
+#include "qkv_rows.h"
 
 #include <cstring>
 
@@ -34,14 +36,9 @@ constexpr int ROWB = D * 2;  // bytes per LDS image row
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-// 16-byte chunk swizzle of the [rows][128] bf16 images (256-B rows = one LDS bank row):
-// ch ^ ((row & 3) << 2 | S((row >> 2) & 3)), S = {0, 2, 3, 1}. Checked exhaustively (tools/lds_swizzle_check.py)
-// against the MI355X lane groups: conflict-free for the 16-B row reads (ds_read_b128 groups
-// {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...) AND for the transposed ds_read_b64_tr_b16 reads (2 x 32 lanes);
-// the previous S(q) = q was 2-way on both.
-__device__ __forceinline__ int swz(int row, int ch) {
-  return ch ^ (((row & 3) << 2) | ((0x78 >> (2 * ((row >> 2) & 3))) & 3));
-}
+// 16-byte chunk swizzle of the [rows][128] bf16 images (256-B rows = one LDS bank row): swz256_s (gemm_prims.h),
+// conflict-free for the 16-B row reads AND for the transposed ds_read_b64_tr_b16 reads.
+__device__ __forceinline__ int swz(int row, int ch) { return swz256_s(row, ch); }
 __device__ __forceinline__ int img_off(int row, int ch) { return row * ROWB + 16 * swz(row, ch); }
 
 __device__ __forceinline__ f32x4 mfma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
@@ -132,22 +129,11 @@ struct Offs {
   }
 };
 
-__device__ __forceinline__ bf16x8 lds_row(const char* base, int off) { return *(const bf16x8*)(base + off); }
-
-__device__ __forceinline__ bf16x8 lds_tr(const char* base, int off) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s4;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + off));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + off + 16 * ROWB));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 // vmcnt(0) as the builtin (not inline asm), so the waitcnt pass sees it: a kernel whose loop-invariant operands (Q /
 // K fragments) are global loads issued before the loop must drain them there; otherwise the pass merges the loop-entry
 // state with the back edge and puts a vmcnt(0) before the loop's first MFMA, which also waits for the NEXT tile's
 // prefetch every iteration (its latency fully exposed: profiles/r3_attention.md).
-__device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+__device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 15)); }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // v_max3_f32 (fmaxf's NaN canonicalisation doubles the VALU count; scores are finite or -inf here)
@@ -184,15 +170,11 @@ struct Stage {
 // Buffer-descriptor forms (the 32x32 kernels): the tile's base and byte range in a wave-uniform descriptor, the lane's
 // row / chunk in a loop-invariant VGPR offset, the tile's row offset in an SGPR. Rows past the sequence end fall
 // outside the range and read as ZERO (no clamps, no per-row branches, no 64-bit VALU address math per piece).
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void* p, long bytes) {
   const unsigned long long a = (unsigned long long)p;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
   const unsigned n = __builtin_amdgcn_readfirstlane((unsigned)(bytes < 0 ? 0 : bytes));
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
-__device__ __forceinline__ void bdma16(rsrc_t r, char* dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
 }
 __device__ __forceinline__ bf16x8 bload16(rsrc_t r, unsigned voff) {
   const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
@@ -234,10 +216,8 @@ struct Offs32 {
 };
 
 __device__ __forceinline__ bf16x8 lds_tr2(const char* base, int lo, int hi) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s4;
   s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + lo));
   s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + hi));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
   s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
   return __builtin_bit_cast(bf16x8, v);
 }
@@ -292,8 +272,8 @@ __device__ __forceinline__ void fwd32_step(const char* __restrict__ cur, char* _
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned so = (unsigned)(k0 + 64 + 16 * j) * rowb;
-      bdma16(kv, nxt + (wave + 4 * j) * 1024, voffk, so);
-      bdma16(kv, nxt + TB + (wave + 4 * j) * 1024, voffv, so);
+      bldsx4(kv, nxt + (wave + 4 * j) * 1024, voffk, so);
+      bldsx4(kv, nxt + TB + (wave + 4 * j) * 1024, voffv, so);
     }
   }
   if (k0 > lastkey) return;
@@ -398,8 +378,8 @@ __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ q
   const unsigned voffk = (unsigned)r0 * rowb + 16 * swz(r0, lane & 15), voffv = voffk + nkv * ROWB;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    bdma16(kv, smem + (wave + 4 * j) * 1024, voffk, 16 * j * rowb);
-    bdma16(kv, smem + TB + (wave + 4 * j) * 1024, voffv, 16 * j * rowb);
+    bldsx4(kv, smem + (wave + 4 * j) * 1024, voffk, 16 * j * rowb);
+    bldsx4(kv, smem + TB + (wave + 4 * j) * 1024, voffv, 16 * j * rowb);
   }
   vm_drain();
   f32x16 o[4];
@@ -514,7 +494,7 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
       for (int ks = 0; ks < 2; ++ks) {
         const bf16x8 db = pack_acc(dp[2 * ks], dp[2 * ks + 1]);
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) dq[dt] = mfma(lds_tr(Ks, off.tr[dt] + ks * 32 * ROWB), db, dq[dt]);
+        for (int dt = 0; dt < 8; ++dt) dq[dt] = mfma(lds_tr<16 * ROWB>(Ks, off.tr[dt] + ks * 32 * ROWB), db, dq[dt]);
       }
     }
     if (pre) {
@@ -566,8 +546,8 @@ __device__ __forceinline__ void dq32_step(const char* __restrict__ cur, char* __
               // rows past the sequence end read as zero (outside the descriptors' ranges)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      bdma16(kr, nxt + (wave + 4 * j) * 1024, voffk, (unsigned)(k0n + 16 * j) * rowb);
-      bdma16(sr, nxt + TB + wave * SB + j * 1024, voffs, (unsigned)(k0n + 16 * j) * rows);
+      bldsx4(kr, nxt + (wave + 4 * j) * 1024, voffk, (unsigned)(k0n + 16 * j) * rowb);
+      bldsx4(sr, nxt + TB + wave * SB + j * 1024, voffs, (unsigned)(k0n + 16 * j) * rows);
     }
   }
   if (!active) return;
@@ -667,8 +647,8 @@ __device__ __forceinline__ void dkdv32_step(const char* __restrict__ cur, char* 
               // end read as zero (outside the descriptors' ranges)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      bdma16(qr, nxt + (wv + 2 * j) * 1024, (j & 1) ? vq1 : vq0, qso + 16 * (j >> 1) * rowb);
-      bdma16(orr, nxt + TB + (wv + 2 * j) * 1024, (j & 1) ? vo1 : vo0, oso + 16 * (j >> 1) * rowo);
+      bldsx4(qr, nxt + (wv + 2 * j) * 1024, (j & 1) ? vq1 : vq0, qso + 16 * (j >> 1) * rowb);
+      bldsx4(orr, nxt + TB + (wv + 2 * j) * 1024, (j & 1) ? vo1 : vo0, oso + 16 * (j >> 1) * rowo);
     }
     if (gl < 64 && lsrc != nullptr) {
       pl = lsrc[gl];
@@ -788,8 +768,8 @@ __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
     const int q0 = qt0 * 64, qv = len - q0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {  // piece j: rows qr0 + 8 j (vq1 / vo1 carry the + 8 of odd j)
-      bdma16(qr, base + (kh + 2 * j) * 1024, (j & 1) ? vq1 : vq0, (unsigned)(q0 + 16 * (j >> 1)) * rowb + h * ROWB);
-      bdma16(orr, base + TB + (kh + 2 * j) * 1024, (j & 1) ? vo1 : vo0, (unsigned)(q0 + 16 * (j >> 1)) * rowo + h * ROWB);
+      bldsx4(qr, base + (kh + 2 * j) * 1024, (j & 1) ? vq1 : vq0, (unsigned)(q0 + 16 * (j >> 1)) * rowb + h * ROWB);
+      bldsx4(orr, base + TB + (kh + 2 * j) * 1024, (j & 1) ? vo1 : vo0, (unsigned)(q0 + 16 * (j >> 1)) * rowo + h * ROWB);
     }
     if (gl < 64) {
       float* Ls = (float*)(base + 2 * TB);
@@ -813,7 +793,7 @@ __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
     const unsigned vv1 = (unsigned)(k0 + vr) * rowb + nkv * ROWB + 16 * swz(vr + 8, lane & 15);
 #pragma unroll
     for (int j = 0; j < 8 / G; ++j)
-      bdma16(kr, smem + G * 2 * GB + (w + 2 * G * j) * 1024, (G == 1 && (j & 1)) ? vv1 : vv0,
+      bldsx4(kr, smem + G * 2 * GB + (w + 2 * G * j) * 1024, (G == 1 && (j & 1)) ? vv1 : vv0,
              (unsigned)(8 * G * j) * rowb);
   }
   vm_drain();
@@ -1028,9 +1008,6 @@ at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Te
   return flash_bwd_impl(dout, qkv, out, lse, cu, max_seqlen, nq, nkv, hd, scale, causal, nullptr, nullptr, rope_done,
                         delta);
 }
-
-void rope_(at::Tensor qkv, const at::Tensor& cos, const at::Tensor& sin, int64_t n_q, int64_t n_kv, int64_t head_dim,
-           bool inverse);  // elementwise.hip
 
 // flash_bwd for a qkv whose q / k heads were rotated (RoPE) by the producing GEMM: returns the gradient w.r.t. the
 // UNROTATED qkv. The inverse rotation rides in the dq / dK epilogues on the default path; otherwise the rope kernel

@@ -3,6 +3,7 @@
 // All accesses are 16-byte vectors (8 x bf16); grids are capped at ~8 blocks/CU and
 // grid-stride the rest (CDNA guide G11).
 #include "common.h"
+#include "qkv_rows.h"
 
 namespace sftamd {
 
@@ -144,18 +145,10 @@ __global__ __launch_bounds__(256) void rope_kernel(u16* __restrict__ qkv, const 
     float a[8], b[8], c[8], s[8], o1[8], o2[8];
     unpack8(*(const uint4*)(base + p), a);
     unpack8(*(const uint4*)(base + half + p), b);
-    const float4* cp = (const float4*)(cosb + m * half + p);
-    const float4* sp = (const float4*)(sinb + m * half + p);
-    *(float4*)&c[0] = cp[0];
-    *(float4*)&c[4] = cp[1];
-    *(float4*)&s[0] = sp[0];
-    *(float4*)&s[4] = sp[1];
+    load8f(cosb + m * half + p, c);
+    load8f(sinb + m * half + p, s);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float si = sign * s[i];
-      o1[i] = a[i] * c[i] - b[i] * si;
-      o2[i] = b[i] * c[i] + a[i] * si;
-    }
+    for (int i = 0; i < 8; ++i) rotate_pair_fwd(a[i], b[i], c[i], sign * s[i], o1[i], o2[i]);
     *(uint4*)(base + p) = pack8(o1);
     *(uint4*)(base + half + p) = pack8(o2);
   }
@@ -163,14 +156,8 @@ __global__ __launch_bounds__(256) void rope_kernel(u16* __restrict__ qkv, const 
 
 void rope_(at::Tensor qkv, const at::Tensor& cos, const at::Tensor& sin, int64_t n_q, int64_t n_kv, int64_t head_dim,
            bool inverse) {
-  SFT_CHECK_BF16(qkv);
-  SFT_CHECK_CONTIG(qkv);
-  SFT_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat, "cos/sin must be fp32");
-  SFT_CHECK(cos.is_contiguous() && sin.is_contiguous(), "cos/sin contiguous");
-  SFT_CHECK(head_dim % 16 == 0, "head_dim must be a multiple of 16");
+  const long M = check_qkv_rows("rope_", qkv, cos, sin, n_q, n_kv, head_dim, false);
   const int ld = qkv.size(-1);
-  const long M = qkv.numel() / ld;
-  SFT_CHECK(cos.numel() == M * head_dim / 2, "cos table shape");
   const int nh = n_q + n_kv;
   if (M == 0) return;
   const long n = M * nh * (head_dim / 16);

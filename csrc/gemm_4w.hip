@@ -46,6 +46,7 @@
 #include <climits>
 
 #include "common.h"
+#include "gemm_prims.h"
 #include "g4_api.h"
 #include "splitk_fixup.h"
 
@@ -60,27 +61,7 @@ constexpr int IMG32 = BK32 * ROWB_T;   // 8 KB
 enum { ROW = 0, TR = 1 };
 
 __device__ __forceinline__ int xt(int row) { return 2 * ((row & 3) | (((row >> 3) & 1) << 2)); }
-__device__ __forceinline__ int sel4(int q) { return (0x78 >> (2 * q)) & 3; }
-
-// LDS-DMA through a buffer descriptor: the tile's base in the (wave-uniform) descriptor, each lane's byte offset in a
-// VGPR fixed for the whole loop, the piece / K-step offset in an SGPR — no per-piece 64-bit VALU address arithmetic
-// (the global_load_lds form cost a v_lshl_add_u64 per piece), as hipBLASLt's MT256x256x64 loop does.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t tile_rsrc(const u16* p) {
-  const unsigned long long a = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0xFFFFFFFFu, 0x00020000);
-}
-__device__ __forceinline__ void bldsx4(rsrc_t r, char* dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
-
-constexpr unsigned waitcnt_imm(int vm, int lgkm) {  // gfx9: vmcnt[3:0] expcnt[6:4] lgkmcnt[11:8] vmcnt[5:4]<<14
-  return (unsigned)((vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14));
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
+// (the ROW image's selector S is swz_sel, the LDS-DMA goes through buffer descriptors: tile_rsrc / bldsx4, gemm_prims.h)
 
 __device__ __forceinline__ void mfma(f32x4& c, const bf16x8& b, const bf16x8& a) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(b), "v"(a));
@@ -98,14 +79,14 @@ struct Op32<ROW> {
   int off;   // fragment 0 (fragment i is 1024 B further)
   __device__ __forceinline__ void init(const u16* base, long ld, int r0, long k0, int w, int lane, int sub) {
     // piece P = w + 4 j: 16 rows 16 P + lr (lr = lane >> 2), slot lane & 3; (row >> 2) & 3 = lr >> 2 for all pieces
-    const int lr = lane >> 2, ch = (lane & 3) ^ sel4(lr >> 2);
+    const int lr = lane >> 2, ch = (lane & 3) ^ swz_sel(lr >> 2);
     r = tile_rsrc(base + (long)r0 * ld + k0);
     voff = (unsigned)(((16 * w + lr) * ld + 8 * ch) * 2);
     jst = (unsigned)(128 * ld);
     koff = 0;
     kmax = 0xFFFFFFFFu;
     const int g = lane >> 4, ii = lane & 15;
-    off = (128 * sub + ii) * 64 + 16 * (g ^ sel4(ii >> 2));
+    off = (128 * sub + ii) * 64 + 16 * (g ^ swz_sel(ii >> 2));
   }
   __device__ __forceinline__ void limit(int nsteps) { kmax = (unsigned)(nsteps - 1) * 2 * BK32; }
   __device__ __forceinline__ void advance() { koff = min(koff + 2 * BK32, kmax); }
@@ -346,15 +327,6 @@ __device__ __forceinline__ void mainloop(char* __restrict__ S0, char* __restrict
   __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));  // the LDS-DMA past the end lands before the LDS is released
 }
 
-__device__ __forceinline__ void tile_origin(int tile, int nbm, int nbn, int group, int& m0, int& n0) {
-  const int per_group = group * nbn;
-  const int grp = tile / per_group, first = grp * group;
-  const int gsz = min(nbm - first, group);
-  const int in = tile - grp * per_group;
-  m0 = (first + in % gsz) * 256;
-  n0 = (in / gsz) * 256;
-}
-
 // One GEMM of a launch: operands, tile grid (nbm x nbn tiles of 256 x 256, GROUP-blocked order), epilogue; park =
 // where this problem's whole tiles put their norm partials past P (a split launch's slabs), 0 = straight into P.
 struct Prob {
@@ -388,8 +360,7 @@ g4_kernel(Probs ps, int kred, int ndp, int splits) {
   const int orig = blockIdx.x;
   int wgid = orig;
   if (orig < ndp) {
-    const int xcd = orig & 7, q8 = ndp >> 3, r8 = ndp & 7;
-    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    wgid = xcd_remap(orig, ndp);
   }
   const int nb_all = kred / (4 * BK32);
   int tile = wgid, sk = 0, p0 = 0, p1 = nb_all;
@@ -451,8 +422,6 @@ g4_kernel(Probs ps, int kred, int ndp, int splits) {
   store_tile(acc, ea, m0 + 128 * wm, n0 + 128 * wn, lane, nrm);
 }
 
-static int group_m() { return 8; }  // GROUP_M tile order
-
 static Prob prob(const u16* A, long lda, const u16* B, long ldb, int M, int N, const Epi& ea, long park) {
   Prob p;
   p.A = A;
@@ -461,7 +430,7 @@ static Prob prob(const u16* A, long lda, const u16* B, long ldb, int M, int N, c
   p.ldb = ldb;
   p.nbm = M / 256;
   p.nbn = N / 256;
-  p.group = std::min(group_m(), p.nbm);
+  p.group = std::min(kTileGroup, p.nbm);
   p.park = park;
   p.ea = ea;
   return p;
@@ -521,7 +490,7 @@ void g4_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& out, bool a
     const long n8 = (long)nsk * 65536 / 8;
     splitk_fixup_kernel<256, 256><<<(unsigned)((n8 + 255) / 256), 256, 0, cur_stream()>>>(
         part.data_ptr<float>(), (u16*)out.data_ptr(), ndp, nsk, splits, K / 256, K, accumulate ? 1 : 0, nrm, N / 256,
-        std::min(g4::group_m(), N / 256));
+        std::min(kTileGroup, N / 256));
     SFT_LAUNCH_CHECK();
   }
 }
@@ -595,7 +564,7 @@ void g4_wgrad_multi(const std::vector<WgradJob>& jobs, int split_all, int split_
     const WgradJob& j = jobs[i];
     const int N = j.dy.size(1), K = j.x.size(1);
     fa[nf] = FixArgs{part[i].data_ptr<float>(), (u16*)j.out.data_ptr(), j.nrm, w[i], sn[i], K / 256, K,
-                     j.acc ? 1 : 0, N / 256, std::min(g4::group_m(), N / 256)};
+                     j.acc ? 1 : 0, N / 256, std::min(kTileGroup, N / 256)};
     bstart[nf++] = nblocks;
     nblocks += sn[i] * 32;
   }
@@ -668,7 +637,7 @@ void g4_dgrad(const at::Tensor& dy, const at::Tensor& w, u16* out, long ldo, con
     const int nsk = tiles - ndp;
     const long n8 = (long)nsk * 65536 / 8;
     splitk_fixup_kernel<256, 256><<<(unsigned)((n8 + 255) / 256), 256, 0, cur_stream()>>>(
-        part.data_ptr<float>(), out, ndp, nsk, splits, nbn, (int)ldo, 0, nullptr, nbm, std::min(g4::group_m(), nbm));
+        part.data_ptr<float>(), out, ndp, nsk, splits, nbn, (int)ldo, 0, nullptr, nbm, std::min(kTileGroup, nbm));
     SFT_LAUNCH_CHECK();
   }
 }

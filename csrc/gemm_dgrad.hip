@@ -26,6 +26,7 @@
 // Epilogue: per 16-row slice of m, the fp32 wave tile is transposed through wave-private LDS ([m][n] rows of
 // TM + 4 floats) so every output / gate / up access is a 16-byte vector along n.
 #include "common.h"
+#include "gemm_prims.h"
 
 #include <type_traits>
 
@@ -40,16 +41,10 @@ constexpr int BROWB = 64;           // B image row: 32 k x bf16
 
 enum { EPI_PLAIN = 0, EPI_SWIGLU_BWD = 1 };
 
-__device__ __forceinline__ int swz_a(int row, int ch) { return ch ^ (((row & 3) << 2) | ((row >> 2) & 3)); }
+// chunk swizzles (gemm_prims.h): the weight image's 256-byte rows, the dY image's 64-byte rows
+__device__ __forceinline__ int swz_a(int row, int ch) { return swz256_q(row, ch); }
 __device__ __forceinline__ int img_a(int row, int ch) { return row * AROWB + 16 * swz_a(row, ch); }
-__device__ __forceinline__ int swz_b(int row, int ch) { return ch ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3); }
-
-__device__ __forceinline__ void glds16(const u16* src, char* dst) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                   (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s4;
+__device__ __forceinline__ int swz_b(int row, int ch) { return swz64(row, ch); }
 
 // The transposed weight read in the natural k order: lane group g holds k = 8 g .. 8 g + 7 of a 32-deep step (lo at
 // row 8 g + qq, hi 4 rows below), so the dY fragment is ONE 16-byte read (bank-conflict-free under swz_b / swz_b2)
@@ -59,14 +54,8 @@ typedef __attribute__((address_space(3))) s16x4 lds_s4;
 __device__ __forceinline__ bf16x8 lds_tr4(const char* base, int off, int offh) {
   s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + off));
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + offh));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
   s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
-}
-
-
-constexpr unsigned waitcnt_imm(int vm, int lgkm) {  // gfx9: vmcnt[3:0] expcnt[6:4] lgkmcnt[11:8] vmcnt[5:4]<<14
-  return (unsigned)((vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14));
 }
 
 template <int BM, int BN, int WM, int WN, int NS_>
@@ -127,16 +116,6 @@ struct Stager {
     advance();
   }
 };
-
-__device__ __forceinline__ char* pick(int i, char* b0, char* b1, char* b2, char* b3, char* b4) {
-  switch (i) {
-    case 0: return b0;
-    case 1: return b1;
-    case 2: return b2;
-    case 3: return b3;
-    default: return b4;
-  }
-}
 
 template <class G, bool SCHED>
 __device__ __forceinline__ void ring_loop(char* __restrict__ b0, char* __restrict__ b1, char* __restrict__ b2,
@@ -293,15 +272,10 @@ __global__ void __launch_bounds__(WM * WN * 64, OCC) dgrad_kernel(const u16* __r
   using G = Cfg<BM, BN, WM, WN, NS>;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int per_group = group * nbm;
-  const int grp = wgid / per_group, first = grp * group;
-  const int gsz = min(nbn - first, group);
-  const int in = wgid - grp * per_group;
-  const int bn = first + in % gsz, bm = in / gsz;
-  const int n0 = bn * BM, m0 = bm * BN;
-  SFT_DASSERT(bn < nbn && bm < nbm);
+  const int wgid = xcd_remap(orig, nwg);
+  int n0, m0;
+  tile_origin<BM, BN>(wgid, nbn, nbm, group, n0, m0);  // GROUP-blocked along n
+  SFT_DASSERT(n0 < nbn * BM && m0 < nbm * BN);
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w - wm * WN;
@@ -345,7 +319,7 @@ __global__ void __launch_bounds__(WM * WN * 64, OCC) dgrad_kernel(const u16* __r
 constexpr int BK2 = 64;
 constexpr int AIMG2 = BK2 * AROWB;  // [64 k][128 n] = 16 KB
 constexpr int BROWB2 = 128;
-__device__ __forceinline__ int swz_b2(int row, int ch) { return ch ^ ((row >> 1) & 7); }
+__device__ __forceinline__ int swz_b2(int row, int ch) { return swz128(row, ch); }
 
 template <int BM, int BN, int WM, int WN>
 struct Cfg2 {
@@ -462,14 +436,9 @@ __global__ void __launch_bounds__(NT) dgrad2_kernel(const u16* __restrict__ dY, 
   using G = Cfg2<BM, BN, WM, WN>;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int per_group = group * nbm;
-  const int grp = wgid / per_group, first = grp * group;
-  const int gsz = min(nbn - first, group);
-  const int in = wgid - grp * per_group;
-  const int bn = first + in % gsz, bm = in / gsz;
-  const int n0 = bn * BM, m0 = bm * BN;
+  const int wgid = xcd_remap(orig, nwg);
+  int n0, m0;
+  tile_origin<BM, BN>(wgid, nbn, nbm, group, n0, m0);  // GROUP-blocked along n
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w - wm * WN;
@@ -501,15 +470,13 @@ __global__ void __launch_bounds__(NT) dgrad2_kernel(const u16* __restrict__ dY, 
 template <int BM, int BN, int WM, int WN, int EPI>
 void launch2(const at::Tensor& dy, const at::Tensor& w, const EpiArgs& ea);
 
-static int group_n() { return 8; }  // GROUP tile order over the output columns
-
 template <int BM, int BN, int WM, int WN, int NS, int EPI, int OCC = 1, bool SCHED = true>
 void launch(const at::Tensor& dy, const at::Tensor& w, const EpiArgs& ea) {
   const int M = dy.size(0), K = dy.size(1), N = w.size(1);
   const int nbn = N / BM, nbm = M / BN;
   dgrad_kernel<BM, BN, WM, WN, NS, EPI, OCC, SCHED><<<nbn * nbm, WM * WN * 64, 0, cur_stream()>>>(
       (const u16*)dy.data_ptr(), (const u16*)w.data_ptr(), K, dy.stride(0), w.stride(0), nbn, nbm,
-      std::min(group_n(), nbn), ea);
+      std::min(kTileGroup, nbn), ea);
   SFT_LAUNCH_CHECK();
 }
 
@@ -519,7 +486,7 @@ void launch2(const at::Tensor& dy, const at::Tensor& w, const EpiArgs& ea) {
   const int nbn = N / BM, nbm = M / BN;
   dgrad2_kernel<BM, BN, WM, WN, EPI><<<nbn * nbm, NT, 0, cur_stream()>>>(
       (const u16*)dy.data_ptr(), (const u16*)w.data_ptr(), K, dy.stride(0), w.stride(0), nbn, nbm,
-      std::min(group_n(), nbn), ea);
+      std::min(kTileGroup, nbn), ea);
   SFT_LAUNCH_CHECK();
 }
 

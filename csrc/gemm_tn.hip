@@ -21,6 +21,7 @@
 // Tile order: XCD-aware bijective remap, then GROUP_M-blocked (8 M-tiles per group) so the ~32
 // tiles an XCD runs at once share A and B slabs in its L2.
 #include "common.h"
+#include "gemm_prims.h"
 
 namespace sftamd {
 namespace tn {
@@ -28,27 +29,11 @@ namespace tn {
 constexpr int NT = 512;
 constexpr int BK = 32;     // k per stage
 constexpr int ROWB = 64;   // bytes per LDS image row
-static int group_m() { return 8; }  // GROUP_M tile order: 8 row blocks share each weight panel
 
 enum { EPI_PLAIN = 0, EPI_SWIGLU = 1, EPI_ROPE = 2 };
 
-// ds_read_b128 is serviced in four NON-contiguous 16-lane groups (/opt/skills/guides/MI355X_MICROARCH.md §LDS:
-// {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...). A fragment read has lane (g = lane>>4, ii = lane&15) at
-// image row R + ii, chunk g: its 16-B slot in the 256-B bank row is 4 (ii & 3) + (g ^ S(ii >> 2)).
-// S = {0, 2, 3, 1} makes the 16 slots of every group distinct (the plain S(q) = q is 2-way).
-__device__ __forceinline__ int swz_sel(int q) { return (0x78 >> (2 * q)) & 3; }
-__device__ __forceinline__ int swz(int row, int ch) { return ch ^ swz_sel((row >> 2) & 3); }
-
-__device__ __forceinline__ void glds16(const u16* src, char* dst) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                   (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8 lds_row(const char* base, int off) { return *(const bf16x8*)(base + off); }
-
-constexpr unsigned waitcnt_imm(int vm, int lgkm) {  // gfx9: vmcnt[3:0] expcnt[6:4] lgkmcnt[11:8] vmcnt[5:4]<<14
-  return (unsigned)((vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14));
-}
+// The 64-byte image rows take swz64 (gemm_prims.h): conflict-free for the 16-lane groups of ds_read_b128.
+__device__ __forceinline__ int swz(int row, int ch) { return swz64(row, ch); }
 
 template <int BM, int BN, int WM, int WN, int NS_>
 struct Cfg {
@@ -110,17 +95,6 @@ struct Stager {
     advance();
   }
 };
-
-__device__ __forceinline__ char* pick(int i, char* b0, char* b1, char* b2, char* b3, char* b4, char* b5) {
-  switch (i) {
-    case 0: return b0;
-    case 1: return b1;
-    case 2: return b2;
-    case 3: return b3;
-    case 4: return b4;
-    default: return b5;
-  }
-}
 
 template <class G, int EPI>
 __device__ __forceinline__ void ring_loop(char* __restrict__ b0, char* __restrict__ b1, char* __restrict__ b2,
@@ -276,14 +250,9 @@ __global__ void __launch_bounds__(NT) tn_kernel(const u16* __restrict__ A, const
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   // XCD-aware bijective remap (consecutive ids share an XCD), then GROUP_M-blocked tile order
   const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int per_group = group * nbn;
-  const int grp = wgid / per_group, first = grp * group;
-  const int gsz = min(nbm - first, group);
-  const int in = wgid - grp * per_group;
-  const int bm = first + in % gsz, bn = in / gsz;
-  const int m0 = bm * BM, n0 = bn * BN;
+  const int wgid = xcd_remap(orig, nwg);
+  int m0, n0;
+  tile_origin<BM, BN>(wgid, nbm, nbn, group, m0, n0);
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w - wm * WN;
@@ -325,7 +294,7 @@ __global__ void __launch_bounds__(NT) tn_kernel(const u16* __restrict__ A, const
 // Swizzle for 128-B rows: chunk ^ ((row >> 1) & 7) — conflict-free for the ds_read_b128 lane groups.
 // ============================================================================================
 constexpr int BK2 = 64, ROWB2 = 128;
-__device__ __forceinline__ int swz2(int row, int ch) { return ch ^ ((row >> 1) & 7); }
+__device__ __forceinline__ int swz2(int row, int ch) { return swz128(row, ch); }
 
 template <int BM, int BN, int WM, int WN, int NS_>
 struct Cfg2 {
@@ -642,14 +611,9 @@ __global__ void __launch_bounds__(WM * WN * 64) tn2_kernel(const u16* __restrict
   using G = Cfg2<BM, BN, WM, WN, NS>;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int per_group = group * nbn;
-  const int grp = wgid / per_group, first = grp * group;
-  const int gsz = min(nbm - first, group);
-  const int in = wgid - grp * per_group;
-  const int bm = first + in % gsz, bn = in / gsz;
-  const int m0 = bm * BM, n0 = bn * BN;
+  const int wgid = xcd_remap(orig, nwg);
+  int m0, n0;
+  tile_origin<BM, BN>(wgid, nbm, nbn, group, m0, n0);
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w - wm * WN;
 
@@ -850,14 +814,9 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
   using G = Cfg2<256, 256, 2, 4, 2>;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int per_group = group * nbn;
-  const int grp = wgid / per_group, first = grp * group;
-  const int gsz = min(nbm - first, group);
-  const int in = wgid - grp * per_group;
-  const int bm = first + in % gsz, bn = in / gsz;
-  const int m0 = bm * 256, n0 = bn * 256;
+  const int wgid = xcd_remap(orig, nwg);
+  int m0, n0;
+  tile_origin(wgid, nbm, nbn, group, m0, n0);
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 2, wn = w & 3;
   const int nk = K / BK2;
@@ -947,13 +906,7 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
 // LDS-DMA of the persistent kernel through buffer descriptors (csrc/gemm_4w.hip, profiles/r3_bwd_gemm_4wave.md): the
 // A tile's rows in a per-tile descriptor, the whole weight in another, each lane's byte offset in a VGPR set once per
 // tile, the piece / K offsets in SGPRs — no per-piece 64-bit VALU address arithmetic in the loop.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-__device__ __forceinline__ rsrc_t tile_rsrc(const u16* p) {
-  const unsigned long long a = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0xFFFFFFFFu, 0x00020000);
-}
 
 template <int EPI>
 struct Stager5 {
@@ -965,12 +918,8 @@ struct Stager5 {
   __device__ __forceinline__ void adv(int k) { kb += 2 * k; }
   __device__ __forceinline__ void piece(char* stage, int w, int j, int koff = 0) {
     char* dst = stage + (w + 4 * j) * 1024;
-    if (j < 8)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, va,
-                                               kb + 2 * koff + j * a32, 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void*)dst, 16, vb,
-                                               kb + 2 * koff + boff[j - 8], 0, 0);
+    if (j < 8) bldsx4(ra, dst, va, kb + 2 * koff + j * a32);
+    else bldsx4(rb, dst, vb, kb + 2 * koff + boff[j - 8]);
   }
 };
 
@@ -1010,15 +959,6 @@ __device__ __forceinline__ void tn5_sub(f32x4 (&acc)[8][8], const bf16x8 (&fa)[8
       }
     }
   }
-}
-
-__device__ __forceinline__ void tn5_coords(int tile, int nbm, int nbn, int group, int& m0, int& n0) {
-  const int per_group = group * nbn;
-  const int grp = tile / per_group, first = grp * group;
-  const int gsz = min(nbm - first, group);
-  const int in = tile - grp * per_group;
-  m0 = (first + in % gsz) * 256;
-  n0 = (in / gsz) * 256;
 }
 
 __device__ __forceinline__ unsigned pack2(float a, float b) { return pk2bf(a, b); }
@@ -1198,7 +1138,7 @@ tn6_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda
 #pragma unroll
   for (int q = 0; q < 8; ++q) st.boff[q] = (unsigned)((long)r6_off<EPI>(q, ea.I) * ldb * 2);
   int m0, n0;
-  tn5_coords(tile, nbm, nbn, group, m0, n0);
+  tile_origin(tile, nbm, nbn, group, m0, n0);
   tn6_stager(st, A, lda, ldb, m0, n0, w, lane);
 #pragma unroll
   for (int j = 0; j < 16; ++j) st.piece(X, w, j);
@@ -1220,7 +1160,7 @@ tn6_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda
     const int next = tile + nx;
     const bool has_next = next < t_end;
     int m1 = m0, n1 = n0;
-    if (has_next) tn5_coords(next, nbm, nbn, group, m1, n1);
+    if (has_next) tile_origin(next, nbm, nbn, group, m1, n1);
     // the K-tile pairs of the persistent main loop (tn5_sub: boundaries, DMA placement and vmcnt accounting)
     auto pair = [&](auto init, auto dma, auto last) {
       constexpr bool IN = decltype(init)::value, DM = decltype(dma)::value, LA = decltype(last)::value;
@@ -1276,7 +1216,7 @@ void launch6(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea,
   SFT_CHECK(ea.ldc % 8 == 0 && ((uintptr_t)ea.C) % 16 == 0, "gemm_tn row-contiguous: 16-byte aligned output rows");
   const int nbm = M / 256, nbn = N / 256, tiles = nbm * nbn;
   const int grid = std::min(tiles, num_cus());
-  const int grp = std::min(group_m(), nbm);
+  const int grp = std::min(kTileGroup, nbm);
   auto A = (const u16*)a.data_ptr();
   auto B = (const u16*)w.data_ptr();
   const long lda = a.stride(0), ldb = w.stride(0);
@@ -1296,7 +1236,7 @@ void launch3(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea)
   const int nbm = M / 256, nbn = N / 256;
   tn3_kernel<EPI, TRC, D><<<nbm * nbn, 512, 0, cur_stream()>>>((const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K,
                                                             a.stride(0), w.stride(0), nbm, nbn,
-                                                            std::min(group_m(), nbm), ea);
+                                                            std::min(kTileGroup, nbm), ea);
   SFT_LAUNCH_CHECK();
 }
 
@@ -1306,7 +1246,7 @@ void launch2(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea)
   const int nbm = M / BM, nbn = N / BN;
   tn2_kernel<BM, BN, WM, WN, NS, EPI, VAR><<<nbm * nbn, WM * WN * 64, 0, cur_stream()>>>(
       (const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K, a.stride(0), w.stride(0), nbm, nbn,
-      std::min(group_m(), nbm), ea);
+      std::min(kTileGroup, nbm), ea);
   SFT_LAUNCH_CHECK();
 }
 
@@ -1316,7 +1256,7 @@ void launch(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea) 
   const int nbm = M / BM, nbn = N / BN;
   tn_kernel<BM, BN, WM, WN, NS, EPI><<<nbm * nbn, NT, 0, cur_stream()>>>(
       (const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K, a.stride(0), w.stride(0), nbm, nbn,
-      std::min(group_m(), nbm), ea);
+      std::min(kTileGroup, nbm), ea);
   SFT_LAUNCH_CHECK();
 }
 

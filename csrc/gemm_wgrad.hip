@@ -22,6 +22,7 @@
 // transposed reads bank-conflict free; v_mfma_f32_16x16x32_bf16; XCD-aware workgroup remap; epilogue through LDS
 // (fp32, padded rows) so the beta-accumulate read-modify-write of the bf16 gradient is 16-byte vectorised.
 #include "common.h"
+#include "gemm_prims.h"
 #include "g4_api.h"
 #include "splitk_fixup.h"
 
@@ -33,23 +34,7 @@ namespace wgrad {
 constexpr int ROWB = 256;             // bytes per LDS image row (128 bf16)
 constexpr int NT = 512;
 
-__device__ __forceinline__ int swz(int row, int ch) { return ch ^ (((row & 3) << 2) | ((row >> 2) & 3)); }
-__device__ __forceinline__ int img_off(int row, int ch) { return row * ROWB + 16 * swz(row, ch); }
-
-typedef __attribute__((address_space(3))) s16x4 lds_s4;
-
-__device__ __forceinline__ bf16x8 lds_tr(const char* base, int off) {
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + off));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + off + 16 * ROWB));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ void glds16(const u16* src, char* dst) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                   (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-}
+__device__ __forceinline__ int img_off(int row, int ch) { return row * ROWB + 16 * swz256_q(row, ch); }
 
 // Epilogue: fp32 wave tile -> LDS (rows padded to TN + 4 floats: conflict-free) -> 16-byte
 // read-modify-write of the bf16 gradient (beta = 1 when accumulating, else plain store).
@@ -141,8 +126,8 @@ struct RStager {
     ldb = K;
     left = nsteps;
     const int r = 4 * wave + (lane >> 4), c = lane & 15;
-    pa = A + (long)(t0 + r) * N + n0 + 8 * swz(r, c);
-    pb = B + (long)(t0 + r) * K + k0 + 8 * swz(r, c);
+    pa = A + (long)(t0 + r) * N + n0 + 8 * swz256_q(r, c);
+    pb = B + (long)(t0 + r) * K + k0 + 8 * swz256_q(r, c);
   }
   // Past the last step the same (valid) rows are fetched again into a slot nobody reads: every
   // step then issues exactly PPW DMAs, so the counted waits are compile-time constants with no
@@ -169,24 +154,9 @@ template <class G>
 __device__ __forceinline__ void rread(const char* base, const int (&offA)[G::FM], const int (&offB)[G::FN],
                                       bf16x8 (&af)[G::FM], bf16x8 (&bf)[G::FN]) {
 #pragma unroll
-  for (int j = 0; j < G::FN; ++j) bf[j] = lds_tr(base, offB[j]);
+  for (int j = 0; j < G::FN; ++j) bf[j] = lds_tr<16 * ROWB>(base, offB[j]);
 #pragma unroll
-  for (int i = 0; i < G::FM; ++i) af[i] = lds_tr(base, offA[i]);
-}
-
-__device__ __forceinline__ char* pick(int i, char* b0, char* b1, char* b2, char* b3, char* b4, char* b5) {
-  switch (i) {
-    case 0: return b0;
-    case 1: return b1;
-    case 2: return b2;
-    case 3: return b3;
-    case 4: return b4;
-    default: return b5;
-  }
-}
-
-constexpr unsigned waitcnt_imm(int vm, int lgkm) {  // gfx9: vmcnt[3:0] expcnt[6:4] lgkmcnt[11:8] vmcnt[5:4]<<14
-  return (unsigned)((vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14));
+  for (int i = 0; i < G::FM; ++i) af[i] = lds_tr<16 * ROWB>(base, offA[i]);
 }
 
 // The stage pointers are separate __restrict__ parameters: once inlined, every ds_read and every
@@ -220,7 +190,7 @@ __device__ __forceinline__ void ring_loop(char* __restrict__ b0, char* __restric
         const char* nxt = pick((u + 1) % NS, b0, b1, b2, b3, b4, b5);
         const int cb = u & 1;
 #pragma unroll
-        for (int j = 0; j < G::FN; ++j) fb[cb ^ 1][j] = lds_tr(nxt, offB[j]);
+        for (int j = 0; j < G::FN; ++j) fb[cb ^ 1][j] = lds_tr<16 * ROWB>(nxt, offB[j]);
         __builtin_amdgcn_s_setprio(1);
         // one LDS-DMA piece after each of the first NIMG fragment rows: the DMA issue cost is
         // spread between MFMA groups instead of stalling every wave right after the barrier
@@ -229,7 +199,7 @@ __device__ __forceinline__ void ring_loop(char* __restrict__ b0, char* __restric
 #pragma unroll
           for (int j = 0; j < G::FN; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[cb][j], acc[i][j], 0, 0, 0);
-          fa[i] = lds_tr(nxt, offA[i]);
+          fa[i] = lds_tr<16 * ROWB>(nxt, offA[i]);
           if (i < G::NIMG) st.piece(dst, i);
           if (SCHED) {
             __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);  // MFMA
@@ -274,8 +244,7 @@ __global__ void __launch_bounds__(NT) ring_kernel(const u16* __restrict__ A, con
   const int orig = blockIdx.x;
   int wgid = orig;
   if (orig < ndp) {
-    const int nd = min(ndp, (int)gridDim.x), xcd = orig & 7, q8 = nd >> 3, r8 = nd & 7;
-    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    wgid = xcd_remap(orig, min(ndp, (int)gridDim.x));
   }
   // Hybrid data-parallel + split-K: workgroups [0, ndp) own whole tiles (direct epilogue); the remaining
   // tiles (the partial last wave) are each split `splits` ways over the token axis — consecutive workgroups,

@@ -1,12 +1,9 @@
 // Per-head QK RMSNorm + RoPE on the packed qkv GEMM output (Qwen3: self_attn.q_norm / k_norm, weight [128] shared by
 // all heads of a layer, applied after the projection and before the rotation), forward and backward, head_dim 128.
 //
-// Lane layout: a head row is 128 bf16 = 256 bytes. Lane l of a wave owns row (l >> 3) of the wave's 8 rows and, with
-// p = (l & 7) * 8, the elements p..p+7 and 64+p..64+p+7 of it: two 16-byte accesses, and every rotate-half pair
-// (x[i], x[i + 64]) sits in ONE lane. A row reduction (sum of squares, the backward's mean) is three xor-shuffle
-// steps (1, 2, 4) inside the 8-lane group. A block (4 waves) covers 32 rows per grid-stride step; p is fixed per
-// lane across steps, so the lane's 2 x 16 norm weights are loaded once. All math is fp32 with one rounding to bf16
-// at the store. No atomics.
+// Lane layout: 8 lanes per head row (qkv_rows.h); the row reductions (sum of squares, the backward's mean) stay inside
+// the 8-lane group. A block (4 waves) covers 32 rows per grid-stride step; p is fixed per lane across steps, so the
+// lane's 2 x 16 norm weights are loaded once. All math is fp32 with one rounding to bf16 at the store. No atomics.
 //
 // The forward keeps the un-normalised q|k columns (qk_raw) for the backward; rstd is NOT stored: the backward
 // recomputes it from qk_raw, which it reads anyway (one more 3-step reduction instead of a [M, heads] tensor).
@@ -15,6 +12,7 @@
 // per-block fp32 partials [blocks, 2, 128]; an ordered second pass (two levels of 32) sums the blocks: bitwise
 // reproducible.
 #include "common.h"
+#include "qkv_rows.h"
 
 namespace sftamd {
 
@@ -24,18 +22,6 @@ constexpr int QN_MAX_BLOCKS = 1024;  // 4 blocks / CU: 6 x 16 B in flight per la
 
 static inline int qn_grid(long rows) {
   return (int)std::max<long>(1, std::min<long>((rows + QN_ROWS - 1) / QN_ROWS, QN_MAX_BLOCKS));
-}
-
-__device__ __forceinline__ float group8_sum(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v;
-}
-
-__device__ __forceinline__ void load8f(const float* p, float* f) {
-  *(float4*)&f[0] = ((const float4*)p)[0];
-  *(float4*)&f[4] = ((const float4*)p)[1];
 }
 
 // raw: [M, nh * 128] copy of the un-normalised q|k columns (nullptr: not written — generation)
@@ -76,8 +62,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(u16* __restrict__
     for (int i = 0; i < 8; ++i) {
       const float n1 = (isq ? wq[i] : wk[i]) * (a[i] * rstd);
       const float n2 = (isq ? wq[8 + i] : wk[8 + i]) * (b[i] * rstd);
-      o1[i] = n1 * c[i] - n2 * s[i];
-      o2[i] = n2 * c[i] + n1 * s[i];
+      rotate_pair_fwd(n1, n2, c[i], s[i], o1[i], o2[i]);
     }
     if (ok) {
       if (raw) {
@@ -133,10 +118,7 @@ __device__ __forceinline__ void qn_bwd_group(u16* __restrict__ dqkv, const u16* 
     float g[16], gw[16];
     float dot = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      g[i] = d1[i] * c[i] + d2[i] * s[i];
-      g[8 + i] = d2[i] * c[i] - d1[i] * s[i];
-    }
+    for (int i = 0; i < 8; ++i) rotate_pair_inv(d1[i], d2[i], c[i], s[i], g[i], g[8 + i]);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       xh[i] *= rstd;
@@ -155,19 +137,7 @@ __device__ __forceinline__ void qn_bwd_group(u16* __restrict__ dqkv, const u16* 
       *(uint4*)(row + 64) = pack8(o + 8);
     }
   }
-  // lanes l, l ^ 8, l ^ 16, l ^ 32 hold the same columns of the wave's 8 row groups
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-#pragma unroll
-    for (int o = 8; o < 64; o <<= 1) acc[i] += __shfl_xor(acc[i], o, 64);
-  }
-  if (lane < 8) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      red[p + i] = acc[i];
-      red[64 + p + i] = acc[8 + i];
-    }
-  }
+  wave_colsum128(acc, red, lane, p);
 }
 
 // dqkv: gradient w.r.t. the rotated q|k (in place -> gradient w.r.t. the raw q|k); part: [gridDim.x, 2, 128] fp32
@@ -215,26 +185,17 @@ __global__ __launch_bounds__(1024) void qk_norm_dw_kernel(const float* __restric
 
 static void qn_check(const at::Tensor& qkv, const at::Tensor& qw, const at::Tensor& kw, const at::Tensor& cos,
                      const at::Tensor& sin, int64_t n_q, int64_t n_kv, int64_t head_dim, long& M, long& rows) {
-  SFT_CHECK_CUDA(qkv);
-  SFT_CHECK_BF16(qkv);
-  SFT_CHECK_CONTIG(qkv);
   SFT_CHECK(head_dim == QN_D, "qk_norm_rope: head_dim must be 128");
   SFT_CHECK(n_q > 0 && n_kv > 0, "qk_norm_rope: head counts");
-  SFT_CHECK(qkv.dim() >= 1 && qkv.size(-1) == (n_q + 2 * n_kv) * QN_D, "qk_norm_rope: qkv row width");
+  M = check_qkv_rows("qk_norm_rope", qkv, cos, sin, n_q, n_kv, head_dim, true);
   SFT_CHECK_BF16(qw);
   SFT_CHECK_BF16(kw);
   SFT_CHECK(qw.is_cuda() && kw.is_cuda() && qw.is_contiguous() && kw.is_contiguous() && qw.numel() == QN_D &&
                 kw.numel() == QN_D,
             "qk_norm_rope: norm weights must be contiguous bf16 [128] on the GPU");
-  SFT_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat,
-            "cos/sin must be fp32 GPU tensors");
-  SFT_CHECK(cos.is_contiguous() && sin.is_contiguous(), "cos/sin contiguous");
-  M = qkv.numel() / qkv.size(-1);
-  SFT_CHECK(cos.numel() == M * (QN_D / 2) && sin.numel() == cos.numel(), "cos table shape");
   rows = M * (n_q + n_kv);
   SFT_CHECK(rows < (1L << 31) - (long)QN_MAX_BLOCKS * QN_ROWS, "qk_norm_rope: too many rows for 32-bit indexing");
-  auto al16 = [](const at::Tensor& t) { return ((uintptr_t)t.data_ptr() & 15) == 0; };
-  SFT_CHECK(al16(qkv) && al16(qw) && al16(kw) && al16(cos) && al16(sin), "qk_norm_rope: 16-byte aligned tensors");
+  SFT_CHECK((((uintptr_t)qw.data_ptr() | (uintptr_t)kw.data_ptr()) & 15) == 0, "qk_norm_rope: 16-byte aligned weights");
 }
 
 at::Tensor qk_norm_rope_fwd(at::Tensor qkv, const at::Tensor& qw, const at::Tensor& kw, const at::Tensor& cos,

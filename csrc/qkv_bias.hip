@@ -1,9 +1,7 @@
 // Learned bias on the q, k and v projections + RoPE on the packed qkv GEMM output (Qwen2 / Qwen2.5:
 // self_attn.{q,k,v}_proj.bias, added after the projection and before the rotation), forward and backward, head_dim 128.
 //
-// Lane layout (that of qk_norm.hip): a head row is 128 bf16 = 256 bytes. Lane l of a wave owns row (l >> 3) of the
-// wave's 8 rows and, with p = (l & 7) * 8, the elements p..p+7 and 64+p..64+p+7 of it: two 16-byte accesses, and every
-// rotate-half pair (x[i], x[i + 64]) sits in ONE lane. The head is fixed per block (blockIdx.y) and the block strides
+// Lane layout: 8 lanes per head row (qkv_rows.h). The head is fixed per block (blockIdx.y) and the block strides
 // over tokens, 32 per step (4 waves x 8 rows), so a lane's 16 columns never change: its 16 bias values are loaded
 // once, and the backward keeps 16 fp32 column sums in registers. Whether the block's head is rotated (q, k) or only
 // biased (v) is uniform over the block. All math is fp32 with one rounding to bf16 at the store. No atomics.
@@ -13,6 +11,7 @@
 // row groups) -> block (LDS, fixed order) into fp32 partials [gridDim.x, heads * 128]; a second kernel adds the
 // partial rows in order: bitwise reproducible. gridDim.x * heads <= 1024 bounds the partials (512 KB).
 #include "common.h"
+#include "qkv_rows.h"
 
 namespace sftamd {
 
@@ -22,11 +21,6 @@ constexpr int QB_MAX_BLOCKS = 1024;  // 4 blocks / CU over all heads; bounds the
 
 static inline int qb_grid_x(long M, long heads) {
   return (int)std::max<long>(1, std::min<long>((M + QB_ROWS - 1) / QB_ROWS, QB_MAX_BLOCKS / heads));
-}
-
-__device__ __forceinline__ void qb_load8f(const float* p, float* f) {
-  *(float4*)&f[0] = ((const float4*)p)[0];
-  *(float4*)&f[4] = ((const float4*)p)[1];
 }
 
 // qkv: [M, ld], ld = gridDim.y * 128; heads [0, n_rot) are rotated after the bias, the others only biased
@@ -53,14 +47,9 @@ __global__ __launch_bounds__(256) void qkv_bias_rope_fwd_kernel(u16* __restrict_
     }
     if (rot) {
       float c[8], s[8];
-      qb_load8f(cosb + (long)m * 64 + p, c);
-      qb_load8f(sinb + (long)m * 64 + p, s);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float t1 = o1[i], t2 = o2[i];
-        o1[i] = t1 * c[i] - t2 * s[i];
-        o2[i] = t2 * c[i] + t1 * s[i];
-      }
+      load8f(cosb + (long)m * 64 + p, c);
+      load8f(sinb + (long)m * 64 + p, s);
+      rotate_half_fwd(o1, o2, c, s, o1, o2);
     }
     *(uint4*)row = pack8(o1);
     *(uint4*)(row + 64) = pack8(o2);
@@ -87,21 +76,17 @@ __global__ __launch_bounds__(256) void qkv_bias_rope_bwd_kernel(u16* __restrict_
     unpack8(*(const uint4*)(row + 64), g + 8);
     if (rot) {
       float c[8], s[8];
-      qb_load8f(cosb + (long)m * 64 + p, c);
-      qb_load8f(sinb + (long)m * 64 + p, s);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d1 = g[i], d2 = g[8 + i];
-        g[i] = d1 * c[i] + d2 * s[i];
-        g[8 + i] = d2 * c[i] - d1 * s[i];
-      }
+      load8f(cosb + (long)m * 64 + p, c);
+      load8f(sinb + (long)m * 64 + p, s);
+      rotate_half_inv(g, g + 8, c, s, g, g + 8);
       *(uint4*)row = pack8(g);
       *(uint4*)(row + 64) = pack8(g + 8);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] += g[i];
   }
-  // every lane is back here: lanes l, l ^ 8, l ^ 16, l ^ 32 hold the same columns of the wave's 8 row groups
+  // every lane is back here. This is wave_colsum128 (qkv_rows.h) written out: behind a call the compiler splits the
+  // block after this kernel's divergent token loop and schedules it differently (profiles/shared_kernel_headers.md)
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
 #pragma unroll
@@ -140,20 +125,10 @@ __global__ __launch_bounds__(256) void qkv_bias_dbias_kernel(const float* __rest
 
 static long qb_check(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin, int64_t n_q, int64_t n_kv,
                      int64_t head_dim) {
-  SFT_CHECK_CUDA(qkv);
-  SFT_CHECK_BF16(qkv);
-  SFT_CHECK_CONTIG(qkv);
   SFT_CHECK(head_dim == QB_D, "qkv_bias_rope: head_dim must be 128");
   SFT_CHECK(n_q > 0 && n_kv > 0 && n_q + 2 * n_kv <= QB_MAX_BLOCKS, "qkv_bias_rope: head counts");
-  SFT_CHECK(qkv.dim() >= 1 && qkv.size(-1) == (n_q + 2 * n_kv) * QB_D, "qkv_bias_rope: qkv row width");
-  SFT_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat,
-            "cos/sin must be fp32 GPU tensors");
-  SFT_CHECK(cos.is_contiguous() && sin.is_contiguous(), "cos/sin contiguous");
-  const long M = qkv.numel() / qkv.size(-1);
-  SFT_CHECK(cos.numel() == M * (QB_D / 2) && sin.numel() == cos.numel(), "cos table shape");
+  const long M = check_qkv_rows("qkv_bias_rope", qkv, cos, sin, n_q, n_kv, head_dim, true);
   SFT_CHECK(M < (1L << 31) - (long)QB_MAX_BLOCKS * QB_ROWS, "qkv_bias_rope: too many rows for 32-bit indexing");
-  auto al16 = [](const at::Tensor& t) { return ((uintptr_t)t.data_ptr() & 15) == 0; };
-  SFT_CHECK(al16(qkv) && al16(cos) && al16(sin), "qkv_bias_rope: 16-byte aligned tensors");
   return M;
 }
 

@@ -225,6 +225,50 @@ def test_rope_integer_operands_bit_exact(D, inverse):
     assert torch.equal(bits(got[:, nh * D:]), bits(qkv[:, nh * D:]))
 
 
+def test_rope_argument_checks():
+    """rope_ goes through the checker of its siblings (csrc/qkv_rows.h): a good call still rotates, the inverse after
+    the forward returns the input, and a call whose 16-byte accesses would leave the tensors or be misaligned raises
+    on the host with the tensor untouched."""
+    M, nq, nkv, D = 3, 2, 1, 128
+    nh, ld = nq + nkv, (nq + 2 * nkv) * D
+    rope = _ext.ops().rope_
+    qkv = randn(M, ld, seed=700)
+    cos, sin = _cos_sin(M, D, 701)
+    qk = qkv[:, : nh * D].view(M, nh, D)
+
+    got = qkv.clone()
+    rope(got, cos, sin, nq, nkv, D, False)
+    want, em = rw.rope_refs(qk, cos, sin, False)
+    want, em = want.reshape(M * nh, D), em.reshape(M * nh, D)
+    bound = rw.row_bound(em, want)
+    worst = assert_blocks_close(got[:, : nh * D].reshape(M * nh, D), want, 1, D, bound, "rope good call")
+    assert torch.equal(bits(got[:, nh * D:]), bits(qkv[:, nh * D:]))
+    report("rope_ good call", worst, bound)
+
+    # the inverse of the rotated bf16 output, emulated with the same two roundings
+    rope(got, cos, sin, nq, nkv, D, True)
+    back = qk.double().reshape(M * nh, D)
+    em2 = rw.rope_refs(em.view(M, nh, D), cos, sin, True)[1].reshape(M * nh, D)
+    bound = rw.row_bound(em2, back)
+    worst = assert_blocks_close(got[:, : nh * D].reshape(M * nh, D), back, 1, D, bound, "rope inverse after forward")
+    assert torch.equal(bits(got[:, nh * D:]), bits(qkv[:, nh * D:]))
+    report("rope_ inverse after forward", worst, bound)
+
+    def refused(x, c, s, msg):
+        before = x.clone()
+        with pytest.raises(RuntimeError, match=msg):
+            rope(x, c, s, nq, nkv, D, False)
+        assert torch.equal(bits(x), bits(before))  # nothing was launched
+
+    refused(qkv.cpu(), cos, sin, "qkv must be")
+    refused(qkv.clone(), cos, sin[: M - 1], "cos table")
+    refused(randn(M, 2 * D, seed=702), cos, sin, "row width")       # narrower than the three rotated heads
+    refused(randn(M, ld + 4, seed=703), cos, sin, "row width")      # rows not a multiple of 16 bytes
+    off1 = torch.zeros(M * ld + 1, dtype=BF16, device=DEV)[1:].view(M, ld)  # contiguous, 2 bytes into its storage
+    assert off1.is_contiguous() and off1.data_ptr() % 16 == 2
+    refused(off1, cos, sin, "aligned")
+
+
 # ------------------------------------------------------------------------------------------------ embedding
 @pytest.mark.parametrize("H", [8, 520, 2560, 4096])
 def test_embedding_fwd_bitwise(H):
