@@ -71,6 +71,8 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("qkv_bias_rope_fwd(Tensor(a!) qkv, Tensor bias, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim) -> ()");
   m.def("qkv_bias_rope_bwd(Tensor(a!) dqkv, Tensor cos, Tensor sin, int n_q, int n_kv, int head_dim) -> Tensor");
   m.def("embedding_fwd(Tensor ids, Tensor weight) -> Tensor");
+  // NEFTune: the gather plus mag[m] * u(m * H + c, seed), u uniform in (-1, 1) from hash_u32 (csrc/elementwise.hip)
+  m.def("embedding_noise_fwd(Tensor ids, Tensor weight, Tensor mag, int seed) -> Tensor");
   m.def("dropout_add(Tensor? a, Tensor b, float p, int seed) -> Tensor");
   m.def("lora_widen(Tensor x, int R, float p, int seed) -> (Tensor, Tensor)");
   m.def("lora_fwd(Tensor x, Tensor A, float s, float p, int seed, int ldX=0, bool save_xd=False, bool swiglu=False) -> (Tensor, Tensor)");
@@ -85,7 +87,8 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("copy2d_batch(Tensor desc, int max_elems) -> ()");
   m.def("embedding_bwd(Tensor dy, Tensor sorted_ids, Tensor perm, Tensor(a!) grad_weight) -> ()");
   // loss
-  m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad) -> Tensor");
+  // label_smoothing e in [0, 1) (HF LabelSmoother) or loss_mode 1 = dft (TRL dft_loss); stats row 0 is the objective
+  m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0) -> Tensor");
   // attention
   m.def("flash_fwd(Tensor qkv, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal) -> (Tensor, Tensor)");
   m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None) -> Tensor");

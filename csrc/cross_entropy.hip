@@ -6,6 +6,9 @@
 // accuracy bit (the TRL training metrics, at no extra pass). Pass 2 re-reads the row (L2 /
 // Infinity-Cache resident: the launch caps the rows in flight, see ce_fwd) and overwrites it IN PLACE with the bf16 gradient
 // (softmax - onehot) * (1/num_items_in_batch): fp32 logits are never materialised.
+//
+// The objective is a template parameter (CE_NLL / CE_SMOOTH / CE_DFT below): label smoothing adds one fp32 sum(x)
+// accumulator to pass 1, DFT one weight broadcast through LDS; the plain instantiation keeps its loop bodies.
 #include "common.h"
 
 #include <climits>
@@ -32,10 +35,16 @@ __device__ __forceinline__ void ce_merge(CEAcc& a, const CEAcc& b) {
   }
 }
 
-template <int CE_U>  // row loads in flight per thread
+// Objectives, per valid row (x the bf16 logits, y the label, p = softmax(x), s = inv_count):
+//   CE_NLL     loss = lse - x_y                          dlogit_i = (p_i - [i == y]) s
+//   CE_SMOOTH  loss = lse - (1 - e) x_y - e sum(x) / V   dlogit_i = (p_i - (1 - e) [i == y] - e / V) s   (HF LabelSmoother)
+//   CE_DFT     loss = w (lse - x_y), w = p_y constant    dlogit_i = w (p_i - [i == y]) s                 (TRL dft_loss)
+constexpr int CE_NLL = 0, CE_SMOOTH = 1, CE_DFT = 2;
+
+template <int CE_U, int MODE>  // row loads in flight per thread, objective
 __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ inv_count, float* __restrict__ stats,
-                                                     int M, int V, int write_grad) {
+                                                     int M, int V, int write_grad, float smooth) {
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
   u16* lr = logits + (long)row * V;
@@ -45,6 +54,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   const int nvec = V / 8;
 
   CEAcc acc{-INFINITY, 0.f, 0.f, -INFINITY, INT_MAX};
+  float sumx = 0.f;  // CE_SMOOTH: sum of the row's logits
   auto accum = [&](const uint4& raw, int v) {
     float x[8];
     unpack8(raw, x);
@@ -61,6 +71,12 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
         b.bv = x[i];
         b.bi = v * 8 + i;
       }
+    }
+    if constexpr (MODE == CE_SMOOTH) {
+      float sv = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sv += x[i];
+      sumx += sv;
     }
     ce_merge(acc, b);
   };
@@ -89,14 +105,29 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   }
   __shared__ CEAcc red[4];
   __shared__ float sh_lse;
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __shared__ float red_sx[4];  // CE_SMOOTH: the waves' sum(x)
+  __shared__ float sh_w;       // CE_DFT: the row's weight p_y
+  if constexpr (MODE == CE_SMOOTH) sumx = wave_sum(sumx);
+  if ((tid & 63) == 0) {
+    red[tid >> 6] = acc;
+    if constexpr (MODE == CE_SMOOTH) red_sx[tid >> 6] = sumx;
+  }
   __syncthreads();
   if (tid == 0) {
     CEAcc a = red[0];
     for (int w = 1; w < 4; ++w) ce_merge(a, red[w]);
     const float lse = a.m + __logf(a.s);
     const float xl = valid ? bf2f(lr[label]) : 0.f;
-    stats[row] = valid ? (lse - xl) : 0.f;
+    if constexpr (MODE == CE_SMOOTH) {
+      const float sx = (red_sx[0] + red_sx[1]) + (red_sx[2] + red_sx[3]);
+      stats[row] = valid ? (lse - (1.f - smooth) * xl - smooth * (sx / (float)V)) : 0.f;
+    } else if constexpr (MODE == CE_DFT) {
+      const float w = valid ? __expf(xl - lse) : 0.f;
+      stats[row] = w * (lse - xl);
+      sh_w = w;
+    } else {
+      stats[row] = valid ? (lse - xl) : 0.f;
+    }
     stats[M + row] = lse;
     stats[2 * M + row] = lse - a.t / a.s;
     stats[3 * M + row] = (valid && a.bi == label) ? 1.f : 0.f;
@@ -105,14 +136,20 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   __syncthreads();
   if (!write_grad) return;
   const float lse = sh_lse;
-  const float scale = valid ? inv_count[0] : 0.f;
+  float scale = valid ? inv_count[0] : 0.f;
+  if constexpr (MODE == CE_DFT) scale *= sh_w;
+  const float hot = MODE == CE_SMOOTH ? 1.f - smooth : 1.f;   // weight of the label's column
+  const float flat = MODE == CE_SMOOTH ? smooth / (float)V : 0.f;  // CE_SMOOTH: weight of every column
   auto grad = [&](const uint4& raw, int v) {
     float x[8];
     unpack8(raw, x);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float p = __expf(x[i] - lse);
-      x[i] = (p - ((v * 8 + i) == label ? 1.f : 0.f)) * scale;
+      if constexpr (MODE == CE_SMOOTH)
+        x[i] = ((p - ((v * 8 + i) == label ? hot : 0.f)) - flat) * scale;
+      else
+        x[i] = (p - ((v * 8 + i) == label ? 1.f : 0.f)) * scale;
     }
     *(uint4*)(lr + (long)v * 8) = pack8(x);
   };
@@ -127,11 +164,32 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   for (; v < nvec; v += 256) grad(*(const uint4*)(lr + (long)v * 8), v);
 }
 
-at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor& inv_count, bool write_grad) {
+// One launch of the MODE instantiation; the dynamic-LDS limit is a per-kernel attribute, so each instantiation that
+// meets a pad above 64 KB raises its own, once.
+constexpr int kMaxPad = 160 * 1024 - 1024;
+
+template <int MODE>
+static void ce_launch(u16* lg, const int64_t* lab, const float* inv, float* stats, int M, int V, bool write_grad,
+                      float smooth, int pad) {
+  if (pad > 64 * 1024) {
+    static bool attr = [] {
+      return hipFuncSetAttribute((const void*)ce_fwd_kernel<4, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kMaxPad) == hipSuccess;
+    }();
+    SFT_CHECK(attr, "ce_fwd: could not raise the dynamic LDS limit");
+  }
+  ce_fwd_kernel<4, MODE><<<M, 256, pad, cur_stream()>>>(lg, lab, inv, stats, M, V, write_grad ? 1 : 0, smooth);
+}
+
+at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor& inv_count, bool write_grad,
+                  double label_smoothing, int64_t loss_mode) {
   SFT_CHECK_BF16(logits);
   SFT_CHECK_CONTIG(logits);
   SFT_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
   SFT_CHECK(inv_count.scalar_type() == at::kFloat && inv_count.is_cuda(), "inv_count must be a fp32 GPU tensor");
+  SFT_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "ce_fwd: label_smoothing must be in [0, 1)");
+  SFT_CHECK(loss_mode == 0 || loss_mode == 1, "ce_fwd: loss_mode 0 (nll) or 1 (dft)");
+  SFT_CHECK(loss_mode == 0 || label_smoothing == 0.0, "ce_fwd: dft takes no label smoothing");
   const int V = logits.size(-1);
   const int M = logits.numel() / V;
   SFT_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
@@ -154,17 +212,13 @@ at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor&
   // The pad passes 64 KB once bpc drops to 2 (V above ~136K: 79 KB at 151,936, 159 KB at 262,144), and a launch above
   // 64 KB of dynamic LDS needs the limit raised first (cu_hog does the same for its 81 KB). Raised once to the largest
   // pad, bpc = 1: with the kernel's static reduction scratch (under 1 KB) the block stays within the CU's 160 KB.
-  constexpr int kMaxPad = 160 * 1024 - 1024;
-  if (pad > 64 * 1024) {
-    static bool attr = [] {
-      return hipFuncSetAttribute((const void*)ce_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxPad) ==
-             hipSuccess;
-    }();
-    SFT_CHECK(attr, "ce_fwd: could not raise the dynamic LDS limit");
-  }
   SFT_CHECK(pad <= kMaxPad, "ce_fwd: LDS pad over the CU's 160 KB");
-  ce_fwd_kernel<4><<<M, 256, pad, cur_stream()>>>(lg, lab.data_ptr<int64_t>(), inv_count.data_ptr<float>(),
-                                                  stats.data_ptr<float>(), M, V, write_grad ? 1 : 0);
+  auto* lb = lab.data_ptr<int64_t>();
+  auto* ic = inv_count.data_ptr<float>();
+  auto* st = stats.data_ptr<float>();
+  if (loss_mode == 1) ce_launch<CE_DFT>(lg, lb, ic, st, M, V, write_grad, 0.f, pad);
+  else if (label_smoothing > 0.0) ce_launch<CE_SMOOTH>(lg, lb, ic, st, M, V, write_grad, (float)label_smoothing, pad);
+  else ce_launch<CE_NLL>(lg, lb, ic, st, M, V, write_grad, 0.f, pad);
   SFT_LAUNCH_CHECK();
   return stats;
 }

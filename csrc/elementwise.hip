@@ -181,6 +181,43 @@ __global__ __launch_bounds__(256) void embedding_fwd_kernel(const int64_t* __res
   }
 }
 
+// NEFTune: the gather plus uniform noise, out[m, c] = bf16(fp32(w[ids[m], c]) + mag[m] * u(m H + c, seed)) with
+// u = (2 (hash_u32 >> 9) + 1 - 2^23) 2^-23: the odd integers of (-2^23, 2^23) scaled by 2^-23, exact in fp32,
+// symmetric about 0 and never 0 or +-1. The product and the sum are two separately rounded fp32 operations (no FMA
+// contraction: noise_add) and the result is rounded once to bf16, so ops/reference.py embedding_noise is bit-equal.
+// Nothing is kept for the backward: the noise is additive. Same layout as the plain gather above.
+__device__ __forceinline__ float noise_add(float x, float a, float u) {
+#pragma clang fp contract(off)  // (__fmul_rn / __fadd_rn are plain * and + to the compiler, and contract)
+  const float p = a * u;
+  return x + p;
+}
+
+__global__ __launch_bounds__(256) void embedding_noise_fwd_kernel(const int64_t* __restrict__ ids,
+                                                                  const u16* __restrict__ w,
+                                                                  const float* __restrict__ mag, u16* __restrict__ out,
+                                                                  long M, int H, long V, unsigned seed) {
+  const int vpr = H / 8;
+  const long n = M * vpr;
+  for (long t = blockIdx.x * 256L + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
+    const long m = t / vpr;
+    const int c = (int)(t - m * vpr) * 8;
+    long id = ids[m];
+    SFT_DASSERT(id >= 0 && id < V);
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    float x[8];
+    unpack8(*(const uint4*)(w + id * H + c), x);
+    const float a = mag[m];
+    const unsigned long long idx = (unsigned long long)m * H + c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = (int)(2u * (hash_u32(idx + i, seed) >> 9) + 1u) - (1 << 23);  // odd, |k| < 2^23
+      const float u = (float)k * 0x1p-23f;                                         // exact
+      x[i] = noise_add(x[i], a, u);
+    }
+    *(uint4*)(out + m * H + c) = pack8(x);
+  }
+}
+
 // One wave per sorted position; the first position of each run of equal ids sums all rows of
 // the run in fp32 (fixed order) and adds the result into the bf16 gradient row: one writer per
 // row, no atomics, bitwise reproducible.
@@ -256,6 +293,27 @@ at::Tensor embedding_fwd(const at::Tensor& ids, const at::Tensor& w) {
   if (M == 0) return out;
   embedding_fwd_kernel<<<ew_grid(M * H / 8), 256, 0, cur_stream()>>>(idc.data_ptr<int64_t>(), (const u16*)w.data_ptr(),
                                                                       (u16*)out.data_ptr(), M, H, w.size(0));
+  SFT_LAUNCH_CHECK();
+  return out;
+}
+
+at::Tensor embedding_noise_fwd(const at::Tensor& ids, const at::Tensor& w, const at::Tensor& mag, int64_t seed) {
+  SFT_CHECK_BF16(w);
+  SFT_CHECK_CONTIG(w);
+  SFT_CHECK(ids.scalar_type() == at::kLong, "ids must be int64");
+  auto idc = ids.contiguous();
+  const int H = w.size(1);
+  SFT_CHECK(H % 8 == 0, "hidden % 8");
+  const long M = idc.numel();
+  SFT_CHECK(mag.is_cuda() && mag.scalar_type() == at::kFloat && mag.is_contiguous() && mag.numel() == M,
+            "embedding_noise_fwd: mag must be a contiguous fp32 GPU tensor with one value per token");
+  auto sizes = idc.sizes().vec();
+  sizes.push_back(H);
+  auto out = at::empty(sizes, w.options());
+  if (M == 0) return out;
+  embedding_noise_fwd_kernel<<<ew_grid(M * H / 8), 256, 0, cur_stream()>>>(
+      idc.data_ptr<int64_t>(), (const u16*)w.data_ptr(), mag.data_ptr<float>(), (u16*)out.data_ptr(), M, H, w.size(0),
+      (unsigned)seed);
   SFT_LAUNCH_CHECK();
   return out;
 }
@@ -415,6 +473,7 @@ TORCH_LIBRARY_IMPL(sftamd, CUDA, m) {
   m.impl("swiglu_bwd", &swiglu_bwd);
   m.impl("rope_", &rope_);
   m.impl("embedding_fwd", &embedding_fwd);
+  m.impl("embedding_noise_fwd", &embedding_noise_fwd);
   m.impl("embedding_bwd", &embedding_bwd);
 }
 

@@ -49,7 +49,8 @@ def main(argv=None):
     ap.add_argument("--config", default=os.getenv("SFT_CONFIG"),
                     help="YAML/JSON file of SFTConfig field overrides (applied over the reference defaults)")
     ap.add_argument("--set", dest="sets", action="append", default=[], metavar="FIELD=VALUE",
-                    help="override one SFTConfig field (repeatable; highest precedence)")
+                    help="override one SFTConfig field (repeatable; highest precedence), e.g. "
+                         "neftune_noise_alpha=5, label_smoothing_factor=0.1 or loss_type=dft")
     ap.add_argument("--merge-lora", action="store_true",
                     help="LoRA runs: write best_model/ with the adapters merged into the weights")
     a = ap.parse_args(argv)

@@ -193,6 +193,10 @@ class CausalLM(nn.Module):
         else:
             self.lm_head = nn.Parameter(torch.empty(cfg.vocab_size, cfg.hidden_size))
         self.gradient_checkpointing = False
+        # NEFTune (SFTTrainer.train sets it from SFTConfig.neftune_noise_alpha and restores 0 when it ends): uniform
+        # noise on the embedding output in training forwards only; neftune_rank is mixed into the per-forward seed
+        self.neftune_noise_alpha = 0.0
+        self.neftune_rank = 0
         inv = ref.rope_inv_freq(cfg.head_dim, cfg.rope_theta, cfg.rope_scaling)
         self.register_buffer("inv_freq", inv, persistent=False)
         self._declare_uses()
@@ -266,6 +270,33 @@ class CausalLM(nn.Module):
             hit = cache[key] = (cu, T, self.rope_tables(torch.arange(T, device=dev).expand(B, T)))
         return hit
 
+    def _neftune_mag(self, cu_seqlens: torch.Tensor, M: int, padded) -> torch.Tensor:
+        """fp32 [M]: alpha / sqrt(L_m * hidden), L_m the length of token m's sequence as attention sees it (its
+        ``cu_seqlens`` segment): T for every row of a padded [B, T] batch, pads included (HF's alpha / sqrt(seq_len *
+        hidden)); the sample's own length in a packed / padding-free batch (the paper's definition; HF on a flattened
+        [1, total] batch would use the total, an artefact of that layout); the global length, local length x group
+        size, under context parallelism. Built on the device, no host sync; a cached constant for the padded shapes
+        of ``_padded_meta``. ``padded`` is (B, T) for such a batch, else None."""
+        alpha, H = float(self.neftune_noise_alpha), self.config.hidden_size
+        group = self.model.layers[0].self_attn.cp_group if len(self.model.layers) else None
+        cp = torch.distributed.get_world_size(group) if group is not None else 1
+        dev = cu_seqlens.device
+        if padded is not None:
+            cache = self.__dict__.setdefault("_neftune_cache", {})
+            key = (padded, str(dev), alpha, cp)
+            hit = cache.get(key)
+            if hit is None:
+                if len(cache) >= 8:
+                    cache.clear()
+                hit = cache[key] = torch.full((M,), alpha / math.sqrt(padded[1] * cp * H), dtype=torch.float32,
+                                              device=dev)
+            return hit
+        cu = cu_seqlens.to(torch.int64)
+        # (rows past the last boundary, if any, form a segment of their own, so the lengths always sum to M)
+        lens = torch.cat([cu[1:] - cu[:-1], (M - cu[-1:]).clamp(min=0)])
+        per_seq = alpha * torch.rsqrt(lens.clamp(min=1).to(torch.float32) * float(cp * H))
+        return torch.repeat_interleave(per_seq, lens, output_size=int(M))
+
     def rope_tables(self, position_ids: torch.Tensor):
         freqs = position_ids.reshape(-1).float()[:, None] * self.inv_freq[None, :].to(position_ids.device)
         return freqs.cos().contiguous(), freqs.sin().contiguous()
@@ -273,16 +304,19 @@ class CausalLM(nn.Module):
     def forward(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None,
                 cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
                 position_ids: Optional[torch.Tensor] = None, num_items_in_batch=None,
-                return_logits: bool = False, shift_labels: bool = True, **_) -> CausalLMOutput:
+                return_logits: bool = False, shift_labels: bool = True, label_smoothing: float = 0.0,
+                loss_type: str = "nll", **_) -> CausalLMOutput:
         """input_ids [B, T] (padded, right) or [M] (packed with cu_seqlens).
 
         ``labels`` are unshifted HF-style labels (-100 ignored) unless ``shift_labels=False``.
         Loss = sum of token CE / num_items_in_batch (HF ``num_items_in_batch`` semantics), or the
-        mean over valid tokens when ``num_items_in_batch`` is None.
+        mean over valid tokens when ``num_items_in_batch`` is None. ``label_smoothing`` (HF ``LabelSmoother``) and
+        ``loss_type="dft"`` (TRL ``dft_loss``) change the per-token objective inside the fused cross-entropy.
         """
         cfg = self.config
         dev = input_ids.device
         rope_cs = None
+        padded = tuple(input_ids.shape) if input_ids.dim() == 2 and cu_seqlens is None else None
         if input_ids.dim() == 2 and cu_seqlens is None and position_ids is None:
             # padded batches of one shape repeat every step: cu_seqlens / RoPE tables are built once
             cu_seqlens, max_seqlen, rope_cs = self._padded_meta(input_ids.shape[0], input_ids.shape[1], dev)
@@ -312,7 +346,11 @@ class CausalLM(nn.Module):
         if rope_cs is None:
             rope_cs = self.rope_tables(position_ids)
 
-        x = ops.embedding(ids, self.model.embed_tokens)
+        if self.training and torch.is_grad_enabled() and (self.neftune_noise_alpha or 0) > 0:
+            x = ops.noisy_embedding(ids, self.model.embed_tokens, self._neftune_mag(cu_seqlens, M, padded),
+                                    ops.neftune_seed(self.neftune_rank))
+        else:
+            x = ops.embedding(ids, self.model.embed_tokens)
         residual = None
         ckpt = self.gradient_checkpointing and self.training and torch.is_grad_enabled()
         # (a layer's o_proj + qkv weight gradients join the previous layer's MLP launch: ops.wgrad_carry_scope)
@@ -337,7 +375,8 @@ class CausalLM(nn.Module):
             else:
                 cnt = torch.tensor(float(num_items_in_batch))
             inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
-            out.loss, out.stats = ops.lm_head_cross_entropy(h, self.lm_head_weight, labels, inv)
+            out.loss, out.stats = ops.lm_head_cross_entropy(h, self.lm_head_weight, labels, inv, label_smoothing,
+                                                            loss_type)
             vf = valid.float()
             out.num_tokens = vf.sum()
             # TRL-style training metrics from the same fused CE pass: [correct, entropy_sum, valid]

@@ -797,6 +797,37 @@ def embedding(ids: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return EmbeddingFn.apply(ids, weight)
 
 
+class NoisyEmbeddingFn(Function):
+    """NEFTune: weight[ids] + mag[m] * u(m * H + c, seed), u uniform in (-1, 1) from the counter hash (HIP:
+    embedding_noise_fwd; twin: ref.embedding_noise, bit-equal). The noise is additive, so nothing is saved for it and
+    the backward is EmbeddingFn's."""
+
+    @staticmethod
+    def forward(ctx, ids, weight, mag, seed):
+        ctx.save_for_backward(ids)
+        ctx.weight = weight
+        if _ext.use_hip(weight):
+            return _ext.ops().embedding_noise_fwd(ids, weight, mag, seed)
+        return ref.embedding_noise(ids, weight, mag, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return EmbeddingFn.backward(ctx, dy) + (None, None)
+
+
+def neftune_seed(rank: int = 0) -> int:
+    """One noise seed per forward pass from torch's CPU generator (as the LoRA dropout seed: the per-rank RNG state is
+    in the checkpoints, so a resumed run redraws it), with the rank mixed in so that data-parallel ranks seeded alike
+    do not share a noise field."""
+    seed = int(torch.randint(1, 2 ** 31 - 1, (1,)).item())
+    return (seed ^ (int(rank) * 0x9E3779B1)) & 0x7FFFFFFF
+
+
+def noisy_embedding(ids: torch.Tensor, weight: torch.Tensor, mag: torch.Tensor, seed: int) -> torch.Tensor:
+    """``embedding`` plus NEFTune noise of per-token magnitude ``mag`` (fp32 [M])."""
+    return NoisyEmbeddingFn.apply(ids, weight, mag, seed)
+
+
 # ----------------------------------------------------------------------------- RMSNorm (+residual)
 class AddRMSNormFn(Function):
     """res_out = x (+ residual); y = rmsnorm(res_out) * w. Returns (y, res_out). y_ld > H (HIP path): y is the left
@@ -1277,18 +1308,21 @@ def qkv_rope_attention(x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, h
 
 
 # ----------------------------------------------------------------------------- LM head + CE
-def _ce_rows(logits: torch.Tensor, labels: torch.Tensor, inv_count: torch.Tensor, write_grad: bool):
-    """Per-row CE over the vocab. Returns stats [4, M] fp32 = (loss, lse, entropy, correct).
+LOSS_MODES = {"nll": 0, "dft": 1}
+
+
+def _ce_rows(logits: torch.Tensor, labels: torch.Tensor, inv_count: torch.Tensor, write_grad: bool,
+             label_smoothing: float = 0.0, loss_mode: int = 0):
+    """Per-row CE over the vocab. Returns stats [4, M] fp32 = (loss, lse, entropy, correct); ``loss`` is the
+    objective's per-row value (label smoothing e, or loss_mode 1 = dft: ref.cross_entropy).
     If write_grad, logits is overwritten in place by d(sum(loss)*inv_count)/dlogits."""
     if _ext.use_hip(logits):
-        return _ext.ops().ce_fwd(logits, labels, inv_count, write_grad)
-    loss, lse, correct, ent = ref.cross_entropy(logits, labels)
+        if label_smoothing == 0 and loss_mode == 0:  # four arguments: also what an older build (SFTAMD_LIB) takes
+            return _ext.ops().ce_fwd(logits, labels, inv_count, write_grad)
+        return _ext.ops().ce_fwd(logits, labels, inv_count, write_grad, float(label_smoothing), int(loss_mode))
+    loss, lse, correct, ent = ref.cross_entropy(logits, labels, label_smoothing, loss_mode)
     if write_grad:
-        valid = (labels != IGNORE_INDEX)
-        p = torch.softmax(logits.float(), -1)
-        p[torch.arange(p.shape[0], device=p.device), labels.clamp(min=0)] -= 1.0
-        p *= (valid.float() * inv_count.float())[:, None]
-        logits.copy_(p)
+        logits.copy_(ref.cross_entropy_grad(logits, labels, inv_count, label_smoothing, loss_mode))
     return torch.stack([loss, lse, ent, correct.float()])
 
 
@@ -1297,11 +1331,11 @@ class LMHeadCEFn(Function):
     (written over the logits buffer), so the fp32 logits are never materialised."""
 
     @staticmethod
-    def forward(ctx, h, weight, labels, inv_count):
+    def forward(ctx, h, weight, labels, inv_count, label_smoothing=0.0, loss_mode=0):
         h2d = h.reshape(-1, h.shape[-1])
         logits = fwd_gemm(h2d, weight) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, weight)
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        stats = _ce_rows(logits, labels.reshape(-1), inv_count, need_grad)
+        stats = _ce_rows(logits, labels.reshape(-1), inv_count, need_grad, label_smoothing, loss_mode)
         loss = (stats[0].sum() * inv_count.float()).reshape(())
         if need_grad:
             ctx.save_for_backward(h2d, logits)
@@ -1326,11 +1360,19 @@ class LMHeadCEFn(Function):
             dh = dh.view(ctx.h_shape)
         if ctx.needs_input_grad[1]:
             dw = _accumulate_weight_grad(w, dlogits, h2d, scale=g)
-        return dh, dw, None, None
+        return dh, dw, None, None, None, None
 
 
-def lm_head_cross_entropy(h, weight, labels, inv_count) -> Tuple[torch.Tensor, torch.Tensor]:
-    return LMHeadCEFn.apply(h, weight, labels, inv_count)
+def lm_head_cross_entropy(h, weight, labels, inv_count, label_smoothing: float = 0.0,
+                          loss_type: str = "nll") -> Tuple[torch.Tensor, torch.Tensor]:
+    """``label_smoothing`` e in [0, 1): HF LabelSmoother; ``loss_type`` "dft": TRL dft_loss (not with smoothing)."""
+    if loss_type not in LOSS_MODES:
+        raise ValueError(f"loss_type must be one of {sorted(LOSS_MODES)}, got {loss_type!r}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+    if loss_type == "dft" and label_smoothing > 0:
+        raise ValueError("loss_type='dft' takes no label smoothing")
+    return LMHeadCEFn.apply(h, weight, labels, inv_count, float(label_smoothing), LOSS_MODES[loss_type])
 
 
 # ----------------------------------------------------------------------------- LoRA linear

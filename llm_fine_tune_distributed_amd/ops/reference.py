@@ -148,18 +148,71 @@ def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens:
     return out.view(M, n_q * head_dim)
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor):
-    """Per-token CE in fp32 (ignore_index=-100). Returns (loss_per_token, lse, argmax_correct, entropy)."""
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, loss_mode: int = 0):
+    """Per-token CE in fp32 (ignore_index=-100). Returns (loss_per_token, lse, argmax_correct, entropy).
+
+    The per-token loss is the objective's (twin of csrc/cross_entropy.hip): ``lse - x_y`` by default,
+    ``lse - (1 - e) x_y - e sum(x) / V`` with ``label_smoothing`` e (HF ``LabelSmoother``), ``p_y (lse - x_y)`` with
+    ``loss_mode`` 1 (TRL ``dft_loss``; p_y is a constant of the gradient: see ``cross_entropy_grad``)."""
     lf = logits.float()
     lse = torch.logsumexp(lf, dim=-1)
     valid = labels != IGNORE_INDEX
     safe = labels.clamp(min=0)
     tgt = lf.gather(-1, safe[:, None]).squeeze(-1)
-    loss = torch.where(valid, lse - tgt, torch.zeros_like(lse))
+    if loss_mode == 1:
+        nll = lse - tgt
+        loss = torch.where(valid, torch.exp(-nll) * nll, torch.zeros_like(lse))
+    elif label_smoothing > 0:
+        e = float(label_smoothing)
+        loss = torch.where(valid, lse - (1.0 - e) * tgt - e * lf.mean(-1), torch.zeros_like(lse))
+    else:
+        loss = torch.where(valid, lse - tgt, torch.zeros_like(lse))
     p = torch.softmax(lf, -1)
     entropy = lse - (p * lf).sum(-1)
     correct = (lf.argmax(-1) == labels) & valid
     return loss, lse, correct, entropy
+
+
+def cross_entropy_grad(logits: torch.Tensor, labels: torch.Tensor, scale: torch.Tensor, label_smoothing: float = 0.0,
+                       loss_mode: int = 0) -> torch.Tensor:
+    """d(sum of the per-token objective of ``cross_entropy`` * scale) / dlogits in fp32, zero on ignored rows:
+    (p - onehot) scale, (p - (1 - e) onehot - e / V) scale when smoothed, p_y (p - onehot) scale for dft."""
+    valid = labels != IGNORE_INDEX
+    rows = torch.arange(logits.shape[0], device=logits.device)
+    safe = labels.clamp(min=0)
+    g = torch.softmax(logits.float(), -1)
+    rs = valid.float() * scale.float()
+    if loss_mode == 1:
+        rs = rs * g[rows, safe]
+        g[rows, safe] -= 1.0
+    elif label_smoothing > 0:
+        e = float(label_smoothing)
+        g[rows, safe] -= 1.0 - e
+        g -= e / logits.shape[-1]
+    else:
+        g[rows, safe] -= 1.0
+    g *= rs[:, None]
+    return g
+
+
+def embedding_noise_u(idx: torch.Tensor, seed: int) -> torch.Tensor:
+    """The NEFTune uniform of element index ``idx`` (int64): (2 (hash_u32 >> 9) + 1 - 2^23) 2^-23 in fp32 — the odd
+    integers of (-2^23, 2^23) scaled by 2^-23: exact, symmetric about 0, never 0 or +-1 (twin of
+    csrc/elementwise.hip embedding_noise_fwd_kernel)."""
+    k = 2 * (hash_u32(idx, seed) >> 9) + 1 - (1 << 23)
+    return k.to(torch.float32) * (2.0 ** -23)
+
+
+def embedding_noise(ids: torch.Tensor, weight: torch.Tensor, mag: torch.Tensor, seed: int) -> torch.Tensor:
+    """weight[ids] + mag[m] * u(m * H + c, seed), bit-equal to the HIP kernel on bf16 weights: one fp32 product, one
+    fp32 sum, one rounding to the weight's dtype. ``mag`` is fp32 with one value per token."""
+    H = weight.shape[1]
+    flat = ids.reshape(-1)
+    M = flat.numel()
+    idx = torch.arange(M * H, dtype=torch.int64, device=weight.device).view(M, H)
+    noise = mag.reshape(M, 1).to(torch.float32) * embedding_noise_u(idx, seed)
+    out = (weight[flat].float() + noise).to(weight.dtype)
+    return out.view(*ids.shape, H)
 
 
 def adamw_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,

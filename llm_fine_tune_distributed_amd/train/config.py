@@ -79,6 +79,13 @@ class SFTConfig:
     completion_only_loss: Optional[bool] = None
     assistant_only_loss: bool = False
     average_tokens_across_devices: bool = True
+    # ---- training objective (HF TrainingArguments / TRL SFTConfig names; all off by default)
+    # NEFTune: uniform noise of magnitude alpha / sqrt(sequence length * hidden) on the embedding output, in training
+    # forwards only (None or 0 = off). Label smoothing (HF LabelSmoother) and loss_type "dft" (TRL dft_loss) change
+    # the per-token objective inside the fused cross-entropy; eval_loss is then that objective too.
+    neftune_noise_alpha: Optional[float] = None
+    label_smoothing_factor: float = 0.0
+    loss_type: str = "nll"                  # nll | dft
     # ---- MI355X-native extras
     freeze_policy: str = "full"             # full | last_n_layers | lora
     freeze_last_n_layers: int = 2
@@ -174,6 +181,18 @@ class SFTConfig:
             return -1
         v = self.eval_steps if self.eval_steps is not None else self.logging_steps
         return int(v) if v else None
+
+    def validate_objective(self) -> None:
+        """The objective fields' ranges and the one forbidden combination (checked when the trainer is built)."""
+        a = self.neftune_noise_alpha
+        if a is not None and not float(a) >= 0:
+            raise ValueError(f"neftune_noise_alpha must be None or >= 0, got {a}")
+        if not 0.0 <= float(self.label_smoothing_factor) < 1.0:
+            raise ValueError(f"label_smoothing_factor must be in [0, 1), got {self.label_smoothing_factor}")
+        if self.loss_type not in ("nll", "dft"):
+            raise ValueError(f"loss_type must be 'nll' or 'dft', got {self.loss_type!r}")
+        if self.loss_type == "dft" and self.label_smoothing_factor > 0:
+            raise ValueError("loss_type='dft' cannot be combined with label_smoothing_factor > 0")
 
     def to_dict(self) -> Dict[str, Any]:
         return dataclasses.asdict(self)

@@ -68,6 +68,7 @@ class SFTTrainer:
                  data_collator: Optional[SFTCollator] = None, peft_config: Optional[LoRAConfig] = None,
                  model_init_seed: int = 0):
         self.args = args = args or SFTConfig()
+        args.validate_objective()
         self.dist = setup_distributed(timeout_s=args.ddp_timeout, verbose=False)
         # context parallelism: consecutive ranks form CP groups that share each batch, sequence-sharded
         # (ring attention); data parallelism runs across the groups
@@ -256,6 +257,14 @@ class SFTTrainer:
                           a.prefetch_batches)
 
     # ------------------------------------------------------------------ core step
+    def _objective(self) -> Dict:
+        """The loss options of SFTConfig as CausalLM.forward takes them (training and evaluation alike: as in HF's
+        compute_loss and TRL's dft_loss, eval_loss is the objective)."""
+        a = self.args
+        if not a.label_smoothing_factor and a.loss_type == "nll":
+            return {}
+        return {"label_smoothing": float(a.label_smoothing_factor), "loss_type": a.loss_type}
+
     @staticmethod
     def _model_inputs(b: Dict) -> Dict:
         kw = {"input_ids": b["input_ids"], "labels": b["labels"]}
@@ -355,7 +364,7 @@ class SFTTrainer:
                 eng.prepare_backward()
                 beat(self._hb_step, "fwd", micro=i)
                 with self._phase("fwd"):
-                    out = model(**self._model_inputs(b), num_items_in_batch=n_items)
+                    out = model(**self._model_inputs(b), num_items_in_batch=n_items, **self._objective())
                 beat(self._hb_step, "bwd", micro=i)
                 with self._phase("bwd"):
                     out.loss.backward()
@@ -386,7 +395,7 @@ class SFTTrainer:
         for b in loader:
             beat(self._hb_step, "eval")
             b = self._cp_shard(b)
-            out = self.model(**self._model_inputs(b), num_items_in_batch=1.0)
+            out = self.model(**self._model_inputs(b), num_items_in_batch=1.0, **self._objective())
             acc[0] += out.loss
             acc[1:4] += out.metrics
             acc[4] += b["num_samples"] if self.cp_rank == 0 else 0  # a CP group shares its samples
@@ -426,10 +435,14 @@ class SFTTrainer:
         # only rank 0 entered it while the others wait in the barrier); no other rank builds a full host copy
         osd = self.optimizer.state_dict(dst=0)
         barrier()
-        ckpt.save_rng(path, self.dist.rank)
         ckpt.save_checkpoint(path, self.model, self.optimizer, self.scheduler, self.state, a, self.dist.rank,
                              tokenizer=self.tokenizer, optimizer_state=osd if self.dist.is_main else {})
         del osd
+        barrier()
+        # after rank 0 has put the directory in place (save_pretrained swaps in a fresh one: a file written into the
+        # path before that is gone): the per-rank generator states, which a resumed run needs to redraw the LoRA
+        # dropout and NEFTune seeds
+        ckpt.save_rng(path, self.dist.rank)
         barrier()
         if self.dist.is_main:
             ckpt.rotate_checkpoints(a.output_dir, a.save_total_limit, self.state.best_model_checkpoint)
@@ -468,9 +481,14 @@ class SFTTrainer:
         """The training loop; the hang watchdog is armed only while it runs (slow phases inside it — checkpoint
         load / save, the first step — under ``Heartbeat.hold``)."""
         self.heartbeat.resume()
+        # NEFTune is on only while train() runs (HF's activate / deactivate): a model saved or queried afterwards is
+        # clean
+        self.model.neftune_noise_alpha = float(self.args.neftune_noise_alpha or 0.0)
+        self.model.neftune_rank = self.dist.rank
         try:
             return self._train(resume_from_checkpoint)
         finally:
+            self.model.neftune_noise_alpha = 0.0
             self.heartbeat.pause()
 
     def _train(self, resume_from_checkpoint: Optional[str] = None) -> TrainOutput:
