@@ -7,141 +7,35 @@
 //               (the down projection's input) — the separate SwiGLU kernel's 540 MB/layer re-read is gone;
 //   EPI_ROPE    qkv projection: rotary embedding of the q and k heads applied before the store.
 // The pairing trick: the B tile's LDS image is filled from permuted WEIGHT ROWS (no weight copy —
-// the stager just points its pieces at other rows) so that MFMA fragments j = 2q and 2q + 1 of a
-// wave hold the two columns the epilogue must combine: (gate c, up c) for SwiGLU, (d, d + 64) of a
-// head for RoPE (rotate_half). Weights keep their HF layout ([gate; up], [q; k; v]).
+// the stager just points its pieces at other rows) so that two MFMA fragments of one wave (2q and
+// 2q + 1 in the 8-wave kernels, j and j + 4 in the persistent one) hold the two columns the epilogue
+// must combine: (gate c, up c) for SwiGLU, (d, d + 64) of a head for RoPE (rotate_half). Weights keep
+// their HF layout ([gate; up], [q; k; v]).
 //
-// Main loop = the ring structure of gemm_wgrad.hip (measured there): 256 x 256 (or 256 x 128) tile
-// per 512-thread workgroup (8 waves, 2x4 / 4x2), BK = 32 per stage, NS stages of global_load_lds
-// in flight (up to all 160 KB of LDS), counted vmcnt + raw s_barrier (one per stage), next-stage
-// fragments read during the current stage's MFMAs, LDS-DMA pieces interleaved with MFMA rows.
-// Operands are K-contiguous, so fragments are plain 16-byte ds_read_b128 rows (no transposed read):
-// LDS image rows are 64 B (32 bf16 of k) with a chunk swizzle (swz below) applied on the GLOBAL
-// source address (glds writes lane-linear) that makes every ds_read_b128 lane group conflict-free.
-// Tile order: XCD-aware bijective remap, then GROUP_M-blocked (8 M-tiles per group) so the ~32
-// tiles an XCD runs at once share A and B slabs in its L2.
+// Three kernel families, one per section below:
+//   ping-pong (tn3_kernel, cfg 11): 256 x 256 tile, 8 waves, the two wave rows one barrier apart.
+//       qkv + RoPE, and the SwiGLU projection when K % 128 != 0. Its plain form is the production qkv
+//       main loop without its epilogue: the tests use it to tell main-loop from epilogue errors.
+//   ring (tn2_kernel): at 256 x 128 the ping-pong's wave-quantisation tail (qkv + RoPE only); at
+//       256 x 256 with the transposed-C epilogue, cfg 5, the ping-pong's predecessor (no route of
+//       ops/fused.py launches it any more).
+//   persistent row-contiguous (tn6_kernel, cfg 60 / 61 = plain / nt stores): 4 waves of 128 x 128, one
+//       workgroup per CU. Plain forwards without a TunableOp selection, the LoRA wide GEMM and the
+//       opt-in SwiGLU projection (its RoPE epilogue is slower in the step than the ping-pong's,
+//       profiles/r5_gemm_fwd.md, and no route selects it).
+// Common to all three: BK = 64, so LDS image rows are 128 B = whole cache lines per global_load_lds
+// row; operands are K-contiguous, so fragments are plain 16-byte ds_read_b128 rows (no transposed
+// read), conflict-free through a chunk swizzle (swz128) applied on the GLOBAL source address (the
+// LDS-DMA writes lane-linear). Tile order: XCD-aware, then GROUP_M-blocked (8 M-tiles per group) so
+// the ~32 tiles an XCD runs at once share A and B slabs in its L2.
+// Measurements: profiles/r1_gemm_tn.md, r2_gemm_pingpong.md, r4_gemm_fwd.md, r5_gemm_fwd.md.
 #include "common.h"
 #include "gemm_prims.h"
 
 namespace sftamd {
 namespace tn {
 
-constexpr int NT = 512;
-constexpr int BK = 32;     // k per stage
-constexpr int ROWB = 64;   // bytes per LDS image row
-
 enum { EPI_PLAIN = 0, EPI_SWIGLU = 1, EPI_ROPE = 2 };
-
-// The 64-byte image rows take swz64 (gemm_prims.h): conflict-free for the 16-lane groups of ds_read_b128.
-__device__ __forceinline__ int swz(int row, int ch) { return swz64(row, ch); }
-
-template <int BM, int BN, int WM, int WN, int NS_>
-struct Cfg {
-  static constexpr int NS = NS_;
-  static constexpr int TM = BM / WM, TN = BN / WN;
-  static constexpr int FM = TM / 16, FN = TN / 16;
-  static constexpr int APIECES = BM / 16, PIECES = (BM + BN) / 16;  // 1 KB = 16 image rows per piece
-  static constexpr int PPW = PIECES / 8;
-  static constexpr int STAGE = (BM + BN) * ROWB;
-  static constexpr int EPI_ROWS = 64, EPI_LD = TN + 4;
-  static constexpr int EPI = 8 * EPI_ROWS * EPI_LD * 4;
-  static constexpr int LDS = (NS * STAGE > EPI) ? NS * STAGE : EPI;
-  static_assert(WM * WN == 8 && PIECES % 8 == 0 && FM >= PPW, "config");
-  static_assert(TN == 64, "epilogue pairing assumes 64-column wave tiles");
-  static_assert(LDS <= 160 * 1024, "LDS budget");
-};
-
-// Global row of the B operand that lands in LDS image rows [16 pb, 16 pb + 16) of a tile.
-template <int EPI, int BN>
-__device__ __forceinline__ int b_piece_row(int pb, int n0, int I) {
-  if constexpr (EPI == EPI_SWIGLU) {
-    // image rows 32q + 16h + r <- gate (h=0) / up (h=1) row c0 + 16q + r; c0 = n0 / 2 (act columns)
-    return (pb & 1) * I + (n0 >> 1) + 16 * (pb >> 1);
-  } else if constexpr (EPI == EPI_ROPE) {
-    // per 128-row head: image rows 32q + 16h + r <- head dim d = 16q + 64h + r
-    const int head = pb >> 3, u = pb & 7;
-    return n0 + 128 * head + 16 * (u >> 1) + 64 * (u & 1);
-  } else {
-    return n0 + 16 * pb;
-  }
-}
-
-// Piece j of wave w is global piece P = w + 8 j (A pieces first). Every piece of a wave is a fixed
-// number of rows away from the wave's first A / first B piece (also for the permuted B rows of the
-// SWIGLU / ROPE tiles), so the stager keeps two lane pointers and compile-time row strides.
-template <int EPI>
-constexpr int b_piece_stride() { return EPI == EPI_SWIGLU ? 64 : 128; }  // rows between B pieces w + 8k
-
-template <class G, int EPI>
-struct Stager {
-  static constexpr int JA = G::APIECES / 8;  // pieces j < JA are A pieces
-  const u16* pa;
-  const u16* pb;
-  long lda, ldb;
-  int left;
-  __device__ __forceinline__ void piece(char* buf, int w, int j) {
-    const u16* src = j < JA ? pa + (long)(128 * j) * lda : pb + (long)(b_piece_stride<EPI>() * (j - JA)) * ldb;
-    glds16(src, buf + (w + 8 * j) * 1024);  // image = A rows then B rows, 1 KB (16 rows) per piece
-  }
-  __device__ __forceinline__ void advance() {
-    if (--left > 0) {
-      pa += BK;
-      pb += BK;
-    }
-  }
-  __device__ __forceinline__ void issue(char* buf, int w) {
-#pragma unroll
-    for (int j = 0; j < G::PPW; ++j) piece(buf, w, j);
-    advance();
-  }
-};
-
-template <class G, int EPI>
-__device__ __forceinline__ void ring_loop(char* __restrict__ b0, char* __restrict__ b1, char* __restrict__ b2,
-                                          char* __restrict__ b3, char* __restrict__ b4, char* __restrict__ b5,
-                                          int nsteps, Stager<G, EPI>& st, int w, int offA, int offB,
-                                          f32x4 (&acc)[G::FM][G::FN]) {
-  constexpr int NS = G::NS, PPW = G::PPW;
-  constexpr int U = (NS % 2) ? 2 * NS : NS;  // stage slot and B register set both compile-time
-  bf16x8 fa[G::FM], fb[2][G::FN];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) st.issue(pick(i, b0, b1, b2, b3, b4, b5), w);
-  __builtin_amdgcn_s_waitcnt(waitcnt_imm((NS - 1) * PPW, 0));
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int j = 0; j < G::FN; ++j) fb[0][j] = lds_row(b0, offB + 1024 * j);
-#pragma unroll
-  for (int i = 0; i < G::FM; ++i) fa[i] = lds_row(b0, offA + 1024 * i);
-  for (int t0 = 0; t0 < nsteps; t0 += U) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (t0 + u < nsteps) {
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm((NS - 2) * PPW, 0));
-        __builtin_amdgcn_s_barrier();
-        char* dst = pick(u % NS, b0, b1, b2, b3, b4, b5);
-        const char* nxt = pick((u + 1) % NS, b0, b1, b2, b3, b4, b5);
-        const int cb = u & 1;
-#pragma unroll
-        for (int j = 0; j < G::FN; ++j) fb[cb ^ 1][j] = lds_row(nxt, offB + 1024 * j);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < G::FM; ++i) {
-#pragma unroll
-          for (int j = 0; j < G::FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[cb][j], acc[i][j], 0, 0, 0);
-          fa[i] = lds_row(nxt, offA + 1024 * i);
-          if (i < PPW) st.piece(dst, w, i);
-          __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);  // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read (one fragment)
-          if (i < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM (the DMA)
-        }
-        st.advance();
-        __builtin_amdgcn_s_setprio(0);
-      }
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));  // drain the tail DMAs before LDS is reused
-}
 
 struct EpiArgs {
   u16* C;        // PLAIN / ROPE: C[M, ldc];  SWIGLU: gu[M, 2I]
@@ -156,141 +50,11 @@ struct EpiArgs {
 __device__ __forceinline__ float silu(float g) { return g / (1.f + __expf(-g)); }
 __device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
 
-// fp32 wave tile -> wave-private LDS rows (TN + 4 floats, conflict-free) -> 16-byte stores.
-template <class G, int EPI>
-__device__ __forceinline__ void epilogue(char* smem, f32x4 (&acc)[G::FM][G::FN], const EpiArgs& ea, int m0, int n0,
-                                         int wm, int wn, int w, int lane) {
-  const int g = lane >> 4, ii = lane & 15;
-  float* ep = reinterpret_cast<float*>(smem) + w * G::EPI_ROWS * G::EPI_LD;
-  constexpr int FPP = G::EPI_ROWS / 16 < G::FM ? G::EPI_ROWS / 16 : G::FM;  // fragment rows per pass
-  constexpr int ROWS = FPP * 16;
-#pragma unroll
-  for (int pass = 0; pass < G::FM / FPP; ++pass) {
-#pragma unroll
-    for (int i = 0; i < FPP; ++i)
-#pragma unroll
-      for (int j = 0; j < G::FN; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ep[(16 * i + 4 * g + e) * G::EPI_LD + 16 * j + ii] = acc[pass * FPP + i][j][e];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private region: writes before reads
-    const int rbase = m0 + wm * G::TM + pass * ROWS;
-    if constexpr (EPI == EPI_PLAIN) {
-      constexpr int SEGS = G::TN / 8;
-#pragma unroll
-      for (int it = 0; it < ROWS * SEGS / 64; ++it) {
-        const int seg = it * 64 + lane, row = seg / SEGS, cs = seg - row * SEGS;
-        const float* pr = ep + row * G::EPI_LD + cs * 8;
-        float v[8];
-        *(float4*)&v[0] = *(const float4*)pr;
-        *(float4*)&v[4] = *(const float4*)(pr + 4);
-        *(uint4*)(ea.C + (long)(rbase + row) * ea.ldc + n0 + wn * G::TN + cs * 8) = pack8(v);
-      }
-    } else {
-      // unit = (row, pair p, half): segment a = cols 32p + 8h (fragment 2p), b = cols 32p + 16 + 8h (2p + 1)
-      constexpr int UPR = G::TN / 16;  // units per row
-#pragma unroll
-      for (int it = 0; it < ROWS * UPR / 64; ++it) {
-        const int un = it * 64 + lane, row = un / UPR, r = un - row * UPR, p = r >> 1, hh = r & 1;
-        const float* pa = ep + row * G::EPI_LD + 32 * p + 8 * hh;
-        float a[8], b[8];
-        *(float4*)&a[0] = *(const float4*)pa;
-        *(float4*)&a[4] = *(const float4*)(pa + 4);
-        *(float4*)&b[0] = *(const float4*)(pa + 16);
-        *(float4*)&b[4] = *(const float4*)(pa + 20);
-        const long grow = rbase + row;
-        const int t = wn * G::TN + 32 * p + 8 * hh;  // image column of segment a
-        if constexpr (EPI == EPI_SWIGLU) {
-          const int c = (n0 >> 1) + 16 * (t >> 5) + 8 * hh;  // act column
-          float o[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            a[e] = rbf(a[e]);  // act from the bf16 gate/up the backward will see
-            b[e] = rbf(b[e]);
-            o[e] = silu(a[e]) * b[e];
-          }
-          u16* gp = ea.C + grow * ea.ldc + c;
-          *(uint4*)gp = pack8(a);
-          *(uint4*)(gp + ea.I) = pack8(b);
-          *(uint4*)(ea.act + grow * ea.I + c) = pack8(o);
-        } else {  // ROPE
-          const int head = t >> 7, u = t & 127, d = 16 * (u >> 5) + 8 * hh;
-          const int col = n0 + 128 * head + d;
-          u16* op = ea.C + grow * ea.ldc + col;
-          if (col < ea.rope_cols) {
-            float cs[8], sn[8], lo[8], hi[8];
-            const float* cp = ea.cosb + grow * 64 + d;
-            const float* sp = ea.sinb + grow * 64 + d;
-            *(float4*)&cs[0] = *(const float4*)cp;
-            *(float4*)&cs[4] = *(const float4*)(cp + 4);
-            *(float4*)&sn[0] = *(const float4*)sp;
-            *(float4*)&sn[4] = *(const float4*)(sp + 4);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float x1 = rbf(a[e]), x2 = rbf(b[e]);  // rope of the bf16 projection (unfused twin)
-              lo[e] = x1 * cs[e] - x2 * sn[e];
-              hi[e] = x2 * cs[e] + x1 * sn[e];
-            }
-            *(uint4*)op = pack8(lo);
-            *(uint4*)(op + 64) = pack8(hi);
-          } else {
-            *(uint4*)op = pack8(a);
-            *(uint4*)(op + 64) = pack8(b);
-          }
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-}
-
-template <int BM, int BN, int WM, int WN, int NS, int EPI>
-__global__ void __launch_bounds__(NT) tn_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda,
-                                                long ldb, int nbm, int nbn, int group, EpiArgs ea) {
-  using G = Cfg<BM, BN, WM, WN, NS>;
-  __shared__ __attribute__((aligned(16))) char smem[G::LDS];
-  // XCD-aware bijective remap (consecutive ids share an XCD), then GROUP_M-blocked tile order
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int wgid = xcd_remap(orig, nwg);
-  int m0, n0;
-  tile_origin<BM, BN>(wgid, nbm, nbn, group, m0, n0);
-
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = w / WN, wn = w - wm * WN;
-
-  Stager<G, EPI> st;
-  st.lda = lda;
-  st.ldb = ldb;
-  st.left = K / BK;
-  {
-    const int lr = lane >> 2, ch = swz(lr, lane & 3);  // row in piece, pre-swizzled chunk
-    st.pa = A + (long)(m0 + 16 * w + lr) * lda + 8 * ch;
-    st.pb = B + (long)(b_piece_row<EPI, BN>(w, n0, ea.I) + lr) * ldb + 8 * ch;
-  }
-  // fragment rows 16 i + ii all share the swizzle of ii (bits 2-3 of the row): fragment i of a wave
-  // is 1 KB after fragment i - 1, an immediate offset of the ds_read
-  const int g = lane >> 4, ii = lane & 15;
-  const int offA = (wm * G::TM + ii) * ROWB + 16 * swz(ii, g);
-  const int offB = (BM + wn * G::TN + ii) * ROWB + 16 * swz(ii, g);
-  f32x4 acc[G::FM][G::FN];
-#pragma unroll
-  for (int i = 0; i < G::FM; ++i)
-#pragma unroll
-    for (int j = 0; j < G::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  char* b[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) b[i] = smem + (i < NS ? i : 0) * G::STAGE;
-  ring_loop<G, EPI>(b[0], b[1], b[2], b[3], b[4], b[5], K / BK, st, w, offA, offB, acc);
-  __syncthreads();
-  epilogue<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
-}
-
 // ============================================================================================
-// BK = 64 variant: 128-byte LDS image rows = whole cache lines per glds row (the BK = 32 ring above
-// fetches every line in two 64-byte halves, one per stage, which costs L2 request bandwidth).
-// Stage = (BM + BN) x 128 B (64 KB at 256 x 256), NS = 2 stages; each stage is consumed in two
-// 32-deep MFMA sub-steps; the only barrier is before the first read of the next stage, after which
-// the DMA of stage t + NS goes into the slot just drained.
+// Ring (256 x 128, NS = 3: the ping-pong kernel's wave tail; 256 x 256, NS = 2: cfg 5): stage =
+// (BM + BN) x 128 B, NS stages of global_load_lds in flight, counted vmcnt + raw s_barrier; each
+// stage is consumed in two 32-deep MFMA sub-steps; the only barrier is before the first read of the
+// next stage, after which the DMA of stage t + NS goes into the slot just drained.
 // Swizzle for 128-B rows: chunk ^ ((row >> 1) & 7) — conflict-free for the ds_read_b128 lane groups.
 // ============================================================================================
 constexpr int BK2 = 64, ROWB2 = 128;
@@ -351,7 +115,8 @@ struct Stager2 {
   }
 };
 
-template <class G, int EPI, bool SCHED = true, bool TRC = false>
+// TRC: transposed C, the B fragment is the MFMA's first operand (epilogue_t)
+template <class G, int EPI, bool TRC>
 __device__ __forceinline__ void ring2_loop(char* __restrict__ b0, char* __restrict__ b1, char* __restrict__ b2,
                                            int nsteps, Stager2<G, EPI>& st, int w, int offA0, int offA1, int offB0,
                                            int offB1, f32x4 (&acc)[G::FM][G::FN]) {
@@ -388,10 +153,6 @@ __device__ __forceinline__ void ring2_loop(char* __restrict__ b0, char* __restri
             acc[i][j] = TRC ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[0][j], fa[i], acc[i][j], 0, 0, 0)
                             : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[0][j], acc[i][j], 0, 0, 0);
           fa[i] = lds_row(cur, offA1 + 2048 * i);
-          if (SCHED) {
-            __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
         }
         __builtin_amdgcn_s_setprio(0);
         // sub-step 1: stage t+1 landed (own DMAs) and every wave is done reading slot t -> barrier,
@@ -412,12 +173,6 @@ __device__ __forceinline__ void ring2_loop(char* __restrict__ b0, char* __restri
           // DMA pieces of stage t + NS spread over the fragment rows (PPW <= 2 FM)
           if (2 * i < PPW) st.piece(cur, w, 2 * i);
           if (2 * i + 1 < PPW) st.piece(cur, w, 2 * i + 1);
-          if (SCHED) {
-            __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (2 * i + 1 < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-            else if (2 * i < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          }
         }
         st.advance();
         __builtin_amdgcn_s_setprio(0);
@@ -427,86 +182,67 @@ __device__ __forceinline__ void ring2_loop(char* __restrict__ b0, char* __restri
   __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
 }
 
-// Early-release variant of ring2_loop (NS = 2): all fragments of a stage's second k-half are read
-// at the start of the stage (32 more VGPRs), so the slot is released — and the DMA of stage t + 2
-// issued into it — half a stage earlier: ~1.5 stages of lead time per DMA instead of 1.
-template <class G, int EPI>
-__device__ __forceinline__ void ring2e_loop(char* __restrict__ b0, char* __restrict__ b1, int nsteps,
-                                            Stager2<G, EPI>& st, int w, int offA0, int offA1, int offB0, int offB1,
-                                            f32x4 (&acc)[G::FM][G::FN]) {
-  constexpr int PPW = G::PPW, H = G::FM / 2;
-  static_assert(G::NS == 2 && PPW <= 2 * H, "early-release ring: 2 stages");
-  bf16x8 fa[G::FM], fa2[G::FM], fb0[G::FN], fb1[G::FN];
+// RoPE epilogue of the ring (natural MFMA operand order): fp32 wave tile -> wave-private LDS rows (TN + 4 floats,
+// conflict-free) -> rotate -> 16-byte stores.
+template <class G>
+__device__ __forceinline__ void rope_tail_epilogue(char* smem, f32x4 (&acc)[G::FM][G::FN], const EpiArgs& ea, int m0,
+                                                   int n0, int wm, int wn, int w, int lane) {
+  const int g = lane >> 4, ii = lane & 15;
+  float* ep = reinterpret_cast<float*>(smem) + w * G::EPI_ROWS * G::EPI_LD;
+  constexpr int FPP = G::EPI_ROWS / 16 < G::FM ? G::EPI_ROWS / 16 : G::FM;  // fragment rows per pass
+  constexpr int ROWS = FPP * 16;
 #pragma unroll
-  for (int j = 0; j < PPW; ++j) st.piece(b0, w, j);
-  st.advance();
+  for (int pass = 0; pass < G::FM / FPP; ++pass) {
 #pragma unroll
-  for (int j = 0; j < PPW; ++j) st.piece(b1, w, j);
-  st.advance();
-  __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW, 0));
-  __builtin_amdgcn_s_barrier();
+    for (int i = 0; i < FPP; ++i)
 #pragma unroll
-  for (int j = 0; j < G::FN; ++j) fb0[j] = lds_row(b0, offB0 + 2048 * j);
+      for (int j = 0; j < G::FN; ++j)
 #pragma unroll
-  for (int i = 0; i < G::FM; ++i) fa[i] = lds_row(b0, offA0 + 2048 * i);
-  for (int t0 = 0; t0 < nsteps; t0 += 2) {
+        for (int e = 0; e < 4; ++e) ep[(16 * i + 4 * g + e) * G::EPI_LD + 16 * j + ii] = acc[pass * FPP + i][j][e];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private region: writes before reads
+    const int rbase = m0 + wm * G::TM + pass * ROWS;
+    // unit = (row, pair p, half): segment a = cols 32p + 8h (fragment 2p), b = cols 32p + 16 + 8h (2p + 1)
+    constexpr int UPR = G::TN / 16;  // units per row
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (t0 + u < nsteps) {
-        char* cur = u == 0 ? b0 : b1;
-        char* nxt = u == 0 ? b1 : b0;
-        // A: read (t, k 32..63); MFMA the first half of (t, k 0..31) while they land
+    for (int it = 0; it < ROWS * UPR / 64; ++it) {
+      const int un = it * 64 + lane, row = un / UPR, r = un - row * UPR, p = r >> 1, hh = r & 1;
+      const float* pa = ep + row * G::EPI_LD + 32 * p + 8 * hh;
+      float a[8], b[8];
+      *(float4*)&a[0] = *(const float4*)pa;
+      *(float4*)&a[4] = *(const float4*)(pa + 4);
+      *(float4*)&b[0] = *(const float4*)(pa + 16);
+      *(float4*)&b[4] = *(const float4*)(pa + 20);
+      const long grow = rbase + row;
+      const int t = wn * G::TN + 32 * p + 8 * hh;  // image column of segment a
+      const int head = t >> 7, u = t & 127, d = 16 * (u >> 5) + 8 * hh;
+      const int col = n0 + 128 * head + d;
+      u16* op = ea.C + grow * ea.ldc + col;
+      if (col < ea.rope_cols) {
+        float cs[8], sn[8], lo[8], hi[8];
+        const float* cp = ea.cosb + grow * 64 + d;
+        const float* sp = ea.sinb + grow * 64 + d;
+        *(float4*)&cs[0] = *(const float4*)cp;
+        *(float4*)&cs[4] = *(const float4*)(cp + 4);
+        *(float4*)&sn[0] = *(const float4*)sp;
+        *(float4*)&sn[4] = *(const float4*)(sp + 4);
 #pragma unroll
-        for (int j = 0; j < G::FN; ++j) fb1[j] = lds_row(cur, offB1 + 2048 * j);
-#pragma unroll
-        for (int i = 0; i < G::FM; ++i) fa2[i] = lds_row(cur, offA1 + 2048 * i);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < H; ++i)
-#pragma unroll
-          for (int j = 0; j < G::FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb0[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW, 0));  // own reads of slot cur done (stage t+1 may fly)
-        __builtin_amdgcn_s_barrier();                     // every wave's reads of slot cur done
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = H; i < G::FM; ++i) {
-#pragma unroll
-          for (int j = 0; j < G::FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb0[j], acc[i][j], 0, 0, 0);
-          const int q = i - H;
-          if (2 * q < PPW) st.piece(cur, w, 2 * q);
-          if (2 * q + 1 < PPW) st.piece(cur, w, 2 * q + 1);
-          __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);
-          if (2 * q + 1 < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-          else if (2 * q < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        for (int e = 0; e < 8; ++e) {
+          const float x1 = rbf(a[e]), x2 = rbf(b[e]);  // rope of the bf16 projection (unfused twin)
+          lo[e] = x1 * cs[e] - x2 * sn[e];
+          hi[e] = x2 * cs[e] + x1 * sn[e];
         }
-        st.advance();
-        __builtin_amdgcn_s_setprio(0);
-        // B: stage t+1 landed (leave stage t+2 in flight); read (t+1, k 0..31) under (t, k 32..63)
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW, 0));
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int j = 0; j < G::FN; ++j) fb0[j] = lds_row(nxt, offB0 + 2048 * j);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < G::FM; ++i) {
-#pragma unroll
-          for (int j = 0; j < G::FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa2[i], fb1[j], acc[i][j], 0, 0, 0);
-          fa[i] = lds_row(nxt, offA0 + 2048 * i);
-          __builtin_amdgcn_sched_group_barrier(0x008, G::FN, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
+        *(uint4*)op = pack8(lo);
+        *(uint4*)(op + 64) = pack8(hi);
+      } else {
+        *(uint4*)op = pack8(a);
+        *(uint4*)(op + 64) = pack8(b);
       }
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
-  __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
 }
 
-// Epilogue of the TRC (transposed-C) build: with the B fragment as the MFMA's first operand, lane
+// Epilogue of the ping-pong kernel (transposed C): with the B fragment as the MFMA's first operand, lane
 // (g, ii) of fragment (i, j) holds output row 16 i + ii, columns 16 j + 4 g .. + 3 — four consecutive
 // columns, so the tile goes to LDS as packed bf16x4 (one ds_write_b64 per fragment instead of four
 // ds_write_b32 of fp32) and back as 16-byte rows for the global stores; the paired fragments (2q,
@@ -605,7 +341,7 @@ __device__ __forceinline__ void epilogue_t(char* smem, f32x4 (&acc)[G::FM][G::FN
   }
 }
 
-template <int BM, int BN, int WM, int WN, int NS, int EPI, int VAR = 0>
+template <int BM, int BN, int WM, int WN, int NS, int EPI, bool TRC>
 __global__ void __launch_bounds__(WM * WN * 64) tn2_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda,
                                                  long ldb, int nbm, int nbn, int group, EpiArgs ea) {
   using G = Cfg2<BM, BN, WM, WN, NS>;
@@ -637,40 +373,37 @@ __global__ void __launch_bounds__(WM * WN * 64) tn2_kernel(const u16* __restrict
   for (int i = 0; i < G::FM; ++i)
 #pragma unroll
     for (int j = 0; j < G::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (VAR == 1)
-    ring2e_loop<G, EPI>(smem, smem + G::STAGE, K / BK2, st, w, offA0, offA1, offB0, offB1, acc);
-  else
-    ring2_loop<G, EPI, VAR == 2, VAR == 3>(smem, smem + G::STAGE, smem + (NS > 2 ? 2 : 0) * G::STAGE, K / BK2, st,
-                                           w, offA0, offA1, offB0, offB1, acc);
+  ring2_loop<G, EPI, TRC>(smem, smem + G::STAGE, smem + (NS > 2 ? 2 : 0) * G::STAGE, K / BK2, st, w, offA0, offA1,
+                          offB0, offB1, acc);
   __syncthreads();
-  if constexpr (VAR == 3)
+  if constexpr (TRC) {
     epilogue_t<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
-  else
-    epilogue<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
+  } else {
+    static_assert(EPI == EPI_ROPE, "natural operand order: the RoPE wave tail only");
+    rope_tail_epilogue<G>(smem, acc, ea, m0, n0, wm, wn, w, lane);
+  }
 }
 
 // ============================================================================================
-// Ping-pong 8-phase schedule (cfg 8 / 9), /opt/skills/guides/cdna_hip_programming.md §5 "The 256² 8-phase template".
-// Same tile (256 x 256, BK = 64, 8 waves of 128 x 64) and the same two 64 KB LDS stages as the BK = 64
-// ring above, but each K-tile runs as FOUR phases, one output quadrant (64 x 32 per wave, 16 MFMAs)
-// each, and the two wave rows run ONE BARRIER APART: while wave row 0 is in a phase's MFMA segment,
-// wave row 1 (its partner on the same SIMD) issues the next phase's LDS reads and DMA, and vice versa
-// — matrix beside memory on every SIMD (/opt/skills/guides/MI355X_MICROARCH.md §Two waves per SIMD). Every phase is
-//   [L: ds_reads of this phase's fragments | DMA of one class of tile t + 2 | counted vmcnt]
-//   lgkmcnt(0); s_barrier; setprio 1; 16 MFMA; setprio 0; s_barrier
+// Ping-pong 8-phase schedule (cfg 11): 256 x 256 tile, BK = 64, 8 waves of 128 x 64, two 64 KB LDS stages.
+// Each K-tile runs as FOUR phases, one output quadrant (64 x 32 per wave, 16 MFMAs) each, and the two
+// wave rows run ONE BARRIER APART: while wave row 0 is in a phase's MFMA segment, wave row 1 (its
+// partner on the same SIMD) issues the next phase's LDS reads and DMA, and vice versa — matrix beside
+// memory on every SIMD. Every phase is
+//   [L: ds_reads of this phase's fragments | DMA of one class | counted vmcnt]
+//   s_barrier; lgkmcnt(0); setprio 1; 16 MFMA; setprio 0; s_barrier
 // The stage is laid out in four 16 KB CLASS images, one per group of fragments read together:
 //   A_lo: tile rows {0..63, 128..191} (fragments i = 0..3 of both wave rows), A_hi: rows +64 (i = 4..7),
-//   B_lo: tile columns 64 q + {0..31} (j = 0, 1 of every wave column), B_hi: columns +32 (j = 2, 3),
-// so each class is released right after the phase that reads it and refilled with tile t + 2 at once:
-//   ph1 reads A_lo + B_lo -> quadrant (A_lo, B_lo);  ph2 reads B_hi, DMA A_lo + B_lo -> (A_lo, B_hi)
-//   ph3 reads A_hi, DMA B_hi -> (A_hi, B_hi);        ph4 DMA A_hi                   -> (A_hi, B_lo)
-// A DMA therefore has ~6-7 phases to land. The class images are separate __restrict__ pointers, so the
+//   B_lo: tile columns 64 q + {0..31} (j = 0, 1 of every wave column), B_hi: columns +32 (j = 2, 3).
+//   ph1 reads A_lo(t) -> quadrant (A_lo, B_lo);  ph2 reads B_hi(t)     -> (A_lo, B_hi)
+//   ph3 reads A_hi(t) -> (A_hi, B_hi);           ph4 reads B_lo(t + 1) -> (A_hi, B_lo)
+// A class is refilled TWO phases after the phase that reads it (the read's lgkmcnt(0) comes after the
+// phase's first barrier, so one phase later is too early: a write-after-read on the staged buffer);
+// pp_tile lists the DMA slots and the waits. The class images are separate __restrict__ pointers, so the
 // compiler's waitcnt pass does not drain the DMA of one class before reading another. Each wave issues
-// 2 DMAs per class in a fixed order, so the vmcnt that retires a class is a compile-time count:
-//   ph1 waits for B_hi(t) (10 younger DMAs), ph2 for A_hi(t) (8), ph4 for A_lo/B_lo(t + 1) (10),
-// always one barrier pair before the read (LDS-DMA data is ordered for other waves only by the
-// issuer's vmcnt followed by a barrier the reader has passed); lgkmcnt(0) BEFORE each phase's first
-// barrier retires the phase's reads, which is what lets the next phase refill that class.
+// 2 DMAs per class in a fixed order, so the vmcnt that retires a class is a compile-time count, always
+// one barrier pair before the read (LDS-DMA data is ordered for other waves only by the issuer's vmcnt
+// followed by a barrier the reader has passed).
 // ============================================================================================
 constexpr int CLS = 16 * 1024;  // class image: 128 rows x 128 B
 __device__ __forceinline__ void wait_vm(int n) {
@@ -713,7 +446,8 @@ struct Stager3 {
   }
 };
 
-template <bool TRC, int I0, int J0>
+// transposed C: the B fragment is the MFMA's first operand (epilogue_t)
+template <int I0, int J0>
 __device__ __forceinline__ void pp_mma(f32x4 (&acc)[8][4], const bf16x8 (&fa)[4][2], const bf16x8 (&fb)[2][2]) {
   __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -722,8 +456,7 @@ __device__ __forceinline__ void pp_mma(f32x4 (&acc)[8][4], const bf16x8 (&fa)[4]
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        acc[I0 + i][J0 + j] = TRC ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], acc[I0 + i][J0 + j], 0, 0, 0)
-                                  : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][s], fb[j][s], acc[I0 + i][J0 + j], 0, 0, 0);
+        acc[I0 + i][J0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], acc[I0 + i][J0 + j], 0, 0, 0);
   __builtin_amdgcn_s_setprio(0);
 }
 
@@ -744,26 +477,22 @@ __device__ __forceinline__ void pp_read_b(const char* img, int offB0, int offB1,
   }
 }
 
-// End of a phase's load segment, then its MFMA segment. D = 1: lgkmcnt(0) before the first barrier
-// (a class may be refilled ONE phase after it is read); D = 2: lgkmcnt(0) after it (refilled two
-// phases after: /opt/skills/guides/cdna_hip_programming.md §5, "Read a staged buffer ... WAR").
-template <int D, bool TRC, int I0, int J0>
+// End of a phase's load segment, then its MFMA segment. lgkmcnt(0) comes after the first barrier, so a class
+// is refilled two phases after it is read, not one.
+template <int I0, int J0>
 __device__ __forceinline__ void pp_phase(f32x4 (&acc)[8][4], const bf16x8 (&fa)[4][2], const bf16x8 (&fb)[2][2]) {
-  if (D == 1) lgkm0();
   bar();
-  if (D == 2) lgkm0();  // also retires phase 4's read of the NEXT tile's B_lo, used only by its phase 1
-  pp_mma<TRC, I0, J0>(acc, fa, fb);
+  lgkm0();  // also retires phase 4's read of the NEXT tile's B_lo, used only by its phase 1
+  pp_mma<I0, J0>(acc, fa, fb);
   bar();
 }
 
 // One K-tile t on stage X (class images xAl, xAh, xBl, xBh); Y = the other stage (tile t + 1).
 // Reads: A_lo(t) in phase 1, B_hi(t) in 2, A_hi(t) in 3, B_lo(t + 1) in 4 (into the other B_lo register
 // set), 8 / 4 / 8 / 4 ds_read_b128 per phase. Each wait retires the class read in the NEXT phase.
-// D = 1 DMA slots: ph1 B_lo(t+2), ph2 A_lo(t+2), ph3 B_hi(t+2), ph4 A_hi(t+2) -> X.
-// D = 2 DMA slots: ph1 A_hi(t+1) -> Y, ph2 B_lo(t+2), ph3 A_lo(t+2), ph4 B_hi(t+2) -> X.
+// DMA slots: ph1 A_hi(t+1) -> Y, ph2 B_lo(t+2), ph3 A_lo(t+2), ph4 B_hi(t+2) -> X.
 // e1 = tile t+1 exists (so tile t-1 issued its slots for t+1), e0 = tile t+2 exists; a wait's count
 // is 2 x the number of this wave's DMA slots issued after the awaited one.
-template <bool TRC, int D>
 __device__ __forceinline__ void pp_tile(char* __restrict__ xAl, char* __restrict__ xAh, char* __restrict__ xBl,
                                         char* __restrict__ xBh, char* __restrict__ yAh, const char* __restrict__ yBl,
                                         int t, int nk, Stager3& st, int w, int offA0, int offA1, int offB0,
@@ -771,44 +500,33 @@ __device__ __forceinline__ void pp_tile(char* __restrict__ xAl, char* __restrict
   const int e1 = t + 1 < nk, e0 = t + 2 < nk;
   bf16x8 fa[4][2], fbh[2][2];
   // phase 1: retire B_hi(t); read A_lo(t)
-  wait_vm(D == 1 ? 2 + 8 * e1 : 2 + 6 * e1);
+  wait_vm(2 + 6 * e1);
   pp_read_a(xAl, offA0, offA1, fa);
-  if (D == 1) {
-    if (e0) st.cls<2>(xBl, w);
-  } else {
-    if (e1) st.cls<1, -1>(yAh, w);
-  }
-  pp_phase<D, TRC, 0, 0>(acc, fa, blc);
+  if (e1) st.cls<1, -1>(yAh, w);
+  pp_phase<0, 0>(acc, fa, blc);
   // phase 2: retire A_hi(t); read B_hi(t)
-  wait_vm(D == 1 ? 8 * e1 + 2 * e0 : 8 * e1);
+  wait_vm(8 * e1);
   pp_read_b(xBh, offB0, offB1, fbh);
-  if (e0) {
-    if (D == 1) st.cls<0>(xAl, w);
-    else st.cls<2>(xBl, w);
-  }
-  pp_phase<D, TRC, 0, 2>(acc, fa, fbh);
+  if (e0) st.cls<2>(xBl, w);
+  pp_phase<0, 2>(acc, fa, fbh);
   // phase 3: retire B_lo(t+1); read A_hi(t)
-  if (e1) wait_vm(D == 1 ? 6 + 4 * e0 : 6 + 2 * e0);
+  if (e1) wait_vm(6 + 2 * e0);
   pp_read_a(xAh, offA0, offA1, fa);
-  if (e0) {
-    if (D == 1) st.cls<3>(xBh, w);
-    else st.cls<0>(xAl, w);
-  }
-  pp_phase<D, TRC, 4, 2>(acc, fa, fbh);
+  if (e0) st.cls<0>(xAl, w);
+  pp_phase<4, 2>(acc, fa, fbh);
   // phase 4: retire A_lo(t+1); read B_lo(t+1)
   if (e1) {
-    wait_vm(D == 1 ? 4 + 6 * e0 : 4 + 4 * e0);
+    wait_vm(4 + 4 * e0);
     pp_read_b(yBl, offB0, offB1, bln);
   }
   if (e0) {
-    if (D == 1) st.cls<1>(xAh, w);
-    else st.cls<3>(xBh, w);
+    st.cls<3>(xBh, w);
     st.advance();
   }
-  pp_phase<D, TRC, 4, 0>(acc, fa, blc);
+  pp_phase<4, 0>(acc, fa, blc);
 }
 
-template <int EPI, bool TRC, int D>
+template <int EPI>
 __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda,
                                                   long ldb, int nbm, int nbn, int group, EpiArgs ea) {
   using G = Cfg2<256, 256, 2, 4, 2>;
@@ -850,8 +568,8 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
 
   char* x0 = smem;
   char* y0 = smem + 4 * CLS;
-  // prologue: the DMA slots tiles -2 and -1 would have issued (class order B_lo, A_lo, B_hi, A_hi; with
-  // D = 2, A_hi(1) is left to phase 1 of tile 0), then B_lo(0) into the first B_lo register set
+  // prologue: the DMA slots tiles -2 and -1 would have issued (class order B_lo, A_lo, B_hi, A_hi; A_hi(1) is
+  // left to phase 1 of tile 0), then B_lo(0) into the first B_lo register set
   st.cls<2>(x0 + 2 * CLS, w);
   st.cls<0>(x0, w);
   st.cls<3>(x0 + 3 * CLS, w);
@@ -861,30 +579,25 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
     st.cls<2>(y0 + 2 * CLS, w);
     st.cls<0>(y0, w);
     st.cls<3>(y0 + 3 * CLS, w);
-    if (D == 1) st.cls<1>(y0 + CLS, w);
   }
   st.advance();
-  wait_vm(nk > 1 ? (D == 1 ? 12 : 10) : 4);  // B_lo(0), A_lo(0)
+  wait_vm(nk > 1 ? 10 : 4);  // B_lo(0), A_lo(0)
   bar();
   bf16x8 bl0[2][2], bl1[2][2];
   pp_read_b(x0 + 2 * CLS, offB0, offB1, bl0);
   lgkm0();
-  if (D == 1) bar();   // phase 1 of tile 0 refills B_lo (D = 1): every wave's read of B_lo(0) retired first
   if (wm == 1) bar();  // wave row 1 runs one barrier behind wave row 0
   for (int t = 0; t < nk; t += 2) {
-    pp_tile<TRC, D>(x0, x0 + CLS, x0 + 2 * CLS, x0 + 3 * CLS, y0 + CLS, y0 + 2 * CLS, t, nk, st, w, offA0, offA1,
-                    offB0, offB1, acc, bl0, bl1);
+    pp_tile(x0, x0 + CLS, x0 + 2 * CLS, x0 + 3 * CLS, y0 + CLS, y0 + 2 * CLS, t, nk, st, w, offA0, offA1, offB0,
+            offB1, acc, bl0, bl1);
     if (t + 1 < nk)
-      pp_tile<TRC, D>(y0, y0 + CLS, y0 + 2 * CLS, y0 + 3 * CLS, x0 + CLS, x0 + 2 * CLS, t + 1, nk, st, w, offA0,
-                      offA1, offB0, offB1, acc, bl1, bl0);
+      pp_tile(y0, y0 + CLS, y0 + 2 * CLS, y0 + 3 * CLS, x0 + CLS, x0 + 2 * CLS, t + 1, nk, st, w, offA0, offA1, offB0,
+              offB1, acc, bl1, bl0);
   }
   if (wm == 0) bar();
   __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
   __syncthreads();
-  if constexpr (TRC)
-    epilogue_t<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
-  else
-    epilogue<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
+  epilogue_t<G, EPI>(smem, acc, ea, m0, n0, wm, wn, w, lane);
 }
 
 // ============================================================================================
@@ -896,9 +609,8 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
 // the GROUP_M order, so the XCD's 32 CUs share A / B panels in its L2), and per tile:
 //   * the NEXT tile's first K-tile is DMA'd into stage X during the last sub-step (both stages are free after the
 //     last barrier: that sub-step's MFMAs need only registers), its second K-tile into Y right after the epilogue;
-//   * the epilogue stores straight from registers: TRC MFMAs (B fragment first) leave each lane 4 consecutive columns
-//     of a row per fragment; v_permlane16_swap between fragment pairs makes that 8 (16 bytes), so a tile is 32
-//     16-byte stores per lane, issued and not waited for (the next tile's MFMAs run while they drain);
+//   * the epilogue stores straight from registers (the row-contiguous section below): a plain tile is 32 16-byte
+//     stores per lane, issued and not waited for (the next tile's MFMAs run while they drain);
 //   * the first sub-step's MFMAs take srcC = 0 (no accumulator zeroing pass).
 // vmcnt bookkeeping (loads and stores share the counter): next K0 (16) < stores (32) < next K1 (16), so "K0 landed"
 // is vmcnt(48) — within the counter's 63.
@@ -908,7 +620,6 @@ __global__ void __launch_bounds__(512) tn3_kernel(const u16* __restrict__ A, con
 // tile, the piece / K offsets in SGPRs — no per-piece 64-bit VALU address arithmetic in the loop.
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-template <int EPI>
 struct Stager5 {
   rsrc_t ra, rb;
   unsigned va, vb;       // lane byte offsets (A: within the tile's rows; B: within the weight)
@@ -924,27 +635,25 @@ struct Stager5 {
 };
 
 template <bool INIT>
-__device__ __forceinline__ void mfma_t(f32x4& c, const bf16x8& b, const bf16x8& a) {
+__device__ __forceinline__ void mfma_t(f32x4& c, const bf16x8& a, const bf16x8& b) {
   if constexpr (INIT)
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(b), "v"(a));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
   else
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(b), "v"(a));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 
-// one sub-step: 8 MFMA groups (fragment row i x 8 B fragments, TRC); READ: the next sub-step's 16 fragments from img;
+// one sub-step: 8 MFMA groups (fragment row i x 8 B fragments); READ: the next sub-step's 16 fragments from img;
 // NP DMA pieces spread over the first DG groups; BAR: the K-tile barrier after group 0
-template <int EPI, bool INIT, bool READ, int NP, bool BAR, int DG = 4, bool ROWC = false>
+template <bool INIT, bool READ, int NP, bool BAR>
 __device__ __forceinline__ void tn5_sub(f32x4 (&acc)[8][8], const bf16x8 (&fa)[8], const bf16x8 (&fb)[8],
                                         bf16x8 (&ra)[8], bf16x8 (&rb)[8], const char* img, int offA, int offB,
-                                        Stager5<EPI>& st, char* dst, int w, char* dst2 = nullptr) {
+                                        Stager5& st, char* dst, int w, char* dst2 = nullptr) {
+  constexpr int DG = 4;
   static_assert(NP % DG == 0 && NP <= 32, "DMA pieces per group");
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if constexpr (ROWC) mfma_t<INIT>(acc[i][j], fa[i], fb[j]);  // A first: rows on the register index
-      else mfma_t<INIT>(acc[i][j], fb[j], fa[i]);                  // TRC: columns on the register index
-    }
+    for (int j = 0; j < 8; ++j) mfma_t<INIT>(acc[i][j], fa[i], fb[j]);  // A first: rows on the register index
     if (BAR && i == 0) __builtin_amdgcn_s_barrier();
     if (READ) {
       ra[i] = lds_row(img, offA + 2048 * i);
@@ -998,7 +707,7 @@ __device__ __forceinline__ int r6_off(int q, int I) {
 }
 
 template <int EPI>
-__device__ __forceinline__ void tn6_stager(Stager5<EPI>& st, const u16* A, long lda, long ldb, int m0, int n0, int w,
+__device__ __forceinline__ void tn6_stager(Stager5& st, const u16* A, long lda, long ldb, int m0, int n0, int w,
                                            int lane) {
   const int lr = lane >> 3, ch = (lane & 7) ^ (4 * (w & 1) + (lr >> 1));
   st.ra = tile_rsrc(A + (long)m0 * lda);
@@ -1132,14 +841,14 @@ tn6_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda
   const int offB0 = rb * ROWB2 + 16 * swz2(rb, g), offB1 = rb * ROWB2 + 16 * swz2(rb, 4 + g);
   char* X = smem;
   char* Y = smem + G::STAGE;
-  Stager5<EPI> st;
+  Stager5 st;
   st.rb = tile_rsrc(B);
   st.a32 = (unsigned)(64 * lda);
 #pragma unroll
   for (int q = 0; q < 8; ++q) st.boff[q] = (unsigned)((long)r6_off<EPI>(q, ea.I) * ldb * 2);
   int m0, n0;
   tile_origin(tile, nbm, nbn, group, m0, n0);
-  tn6_stager(st, A, lda, ldb, m0, n0, w, lane);
+  tn6_stager<EPI>(st, A, lda, ldb, m0, n0, w, lane);
 #pragma unroll
   for (int j = 0; j < 16; ++j) st.piece(X, w, j);
   st.adv(BK2);
@@ -1165,22 +874,22 @@ tn6_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda
     auto pair = [&](auto init, auto dma, auto last) {
       constexpr bool IN = decltype(init)::value, DM = decltype(dma)::value, LA = decltype(last)::value;
       __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
-      tn5_sub<EPI, IN, true, 0, false, 4, true>(acc, a0, b0, a1, b1, X, offA1, offB1, st, X, w);
+      tn5_sub<IN, true, 0, false>(acc, a0, b0, a1, b1, X, offA1, offB1, st, X, w);
       if (IN && !first) {
         __builtin_amdgcn_s_waitcnt(waitcnt_imm(NST, 0));  // K1 landed; the previous tile's stores may still drain
       } else {
         __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
       }
-      tn5_sub<EPI, false, true, DM ? 16 : 0, true, 4, true>(acc, a1, b1, a0, b0, Y, offA0, offB0, st, X, w);
+      tn5_sub<false, true, DM ? 16 : 0, true>(acc, a1, b1, a0, b0, Y, offA0, offB0, st, X, w);
       if (DM) st.adv(BK2);
       __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
-      tn5_sub<EPI, false, true, 0, false, 4, true>(acc, a0, b0, a1, b1, Y, offA1, offB1, st, Y, w);
+      tn5_sub<false, true, 0, false>(acc, a0, b0, a1, b1, Y, offA1, offB1, st, Y, w);
       __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
       if constexpr (LA) {
-        tn6_stager(st, A, lda, ldb, m1, n1, w, lane);
-        tn5_sub<EPI, false, false, 32, true, 4, true>(acc, a1, b1, a0, b0, X, offA0, offB0, st, X, w, Y);
+        tn6_stager<EPI>(st, A, lda, ldb, m1, n1, w, lane);
+        tn5_sub<false, false, 32, true>(acc, a1, b1, a0, b0, X, offA0, offB0, st, X, w, Y);
       } else {
-        tn5_sub<EPI, false, true, 16, true, 4, true>(acc, a1, b1, a0, b0, X, offA0, offB0, st, Y, w);
+        tn5_sub<false, true, 16, true>(acc, a1, b1, a0, b0, X, offA0, offB0, st, Y, w);
         st.adv(BK2);
       }
     };
@@ -1209,11 +918,12 @@ tn6_kernel(const u16* __restrict__ A, const u16* __restrict__ B, int K, long lda
   __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 15));
 }
 
+// cfg 60 / 61 (nt = non-temporal stores)
 template <int EPI>
 void launch6(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea, bool nt) {
   const int M = a.size(0), K = a.size(1);
-  SFT_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, "gemm_tn row-contiguous: M, N % 256, K % 128");
-  SFT_CHECK(ea.ldc % 8 == 0 && ((uintptr_t)ea.C) % 16 == 0, "gemm_tn row-contiguous: 16-byte aligned output rows");
+  SFT_CHECK(K % 128 == 0, "gemm_tn cfg 60 / 61: K % 128 (got K ", K, ")");
+  SFT_CHECK(ea.ldc % 8 == 0 && ((uintptr_t)ea.C) % 16 == 0, "gemm_tn cfg 60 / 61: 16-byte aligned output rows");
   const int nbm = M / 256, nbn = N / 256, tiles = nbm * nbn;
   const int grid = std::min(tiles, num_cus());
   const int grp = std::min(kTileGroup, nbm);
@@ -1230,90 +940,76 @@ void launch6(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea,
   SFT_LAUNCH_CHECK();
 }
 
-template <int EPI, bool TRC, int D = 1>
+// cfg 11
+template <int EPI>
 void launch3(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea) {
   const int M = a.size(0), K = a.size(1);
   const int nbm = M / 256, nbn = N / 256;
-  tn3_kernel<EPI, TRC, D><<<nbm * nbn, 512, 0, cur_stream()>>>((const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K,
-                                                            a.stride(0), w.stride(0), nbm, nbn,
-                                                            std::min(kTileGroup, nbm), ea);
+  tn3_kernel<EPI><<<nbm * nbn, 512, 0, cur_stream()>>>((const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K,
+                                                      a.stride(0), w.stride(0), nbm, nbn, std::min(kTileGroup, nbm),
+                                                      ea);
   SFT_LAUNCH_CHECK();
 }
 
-template <int BM, int BN, int WM, int WN, int NS, int EPI, int VAR = 0>
+// the ring: cfg 5 (256 x 256, 2 stages, transposed C) and the RoPE wave tail (256 x 128, 3 stages, natural order)
+template <int BM, int BN, int WM, int WN, int NS, int EPI, bool TRC>
 void launch2(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea) {
   const int M = a.size(0), K = a.size(1);
   const int nbm = M / BM, nbn = N / BN;
-  tn2_kernel<BM, BN, WM, WN, NS, EPI, VAR><<<nbm * nbn, WM * WN * 64, 0, cur_stream()>>>(
+  tn2_kernel<BM, BN, WM, WN, NS, EPI, TRC><<<nbm * nbn, WM * WN * 64, 0, cur_stream()>>>(
       (const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K, a.stride(0), w.stride(0), nbm, nbn,
       std::min(kTileGroup, nbm), ea);
   SFT_LAUNCH_CHECK();
 }
 
-template <int BM, int BN, int WM, int WN, int NS, int EPI>
-void launch(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea) {
-  const int M = a.size(0), K = a.size(1);
-  const int nbm = M / BM, nbn = N / BN;
-  tn_kernel<BM, BN, WM, WN, NS, EPI><<<nbm * nbn, NT, 0, cur_stream()>>>(
-      (const u16*)a.data_ptr(), (const u16*)w.data_ptr(), K, a.stride(0), w.stride(0), nbm, nbn,
-      std::min(kTileGroup, nbm), ea);
-  SFT_LAUNCH_CHECK();
+// cfg 5, 11 -> the 8-wave kernels; 60, 61 -> the persistent kernel
+template <int EPI>
+void launch_cfg(int64_t cfg, const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea) {
+  if (cfg == 5) launch2<256, 256, 2, 4, 2, EPI, true>(a, w, N, ea);
+  else if (cfg == 11) launch3<EPI>(a, w, N, ea);
+  else launch6<EPI>(a, w, N, ea, cfg == 61);
 }
 
 }  // namespace tn
 
-static void check_tn(const at::Tensor& a, const at::Tensor& w) {
+// Every kernel here works on whole 256 x 256 output tiles and 64-deep K-tiles (cfg 60 / 61: pairs of them, launch6);
+// nothing falls through to another kernel.
+// cfg: 5 = the BK-64 ring with the transposed-C epilogue (the ping-pong's predecessor), 11 = the ping-pong 8-phase
+// schedule (qkv + RoPE, with a 256 x 128 tail launch; SwiGLU when K % 128 != 0; plain for the tests), 60 / 61 = the
+// persistent 4-wave kernel with the row-contiguous store epilogue (plain / nt stores: the plain forwards without a
+// TunableOp selection, the LoRA wide GEMM, the opt-in SwiGLU).
+static void check_tn(const char* op, const at::Tensor& a, const at::Tensor& w, int64_t cfg) {
   SFT_CHECK_CUDA(a);
   SFT_CHECK_BF16(a);
   SFT_CHECK_BF16(w);
-  SFT_CHECK(a.dim() == 2 && w.dim() == 2 && a.size(1) == w.size(1), "gemm_tn: a [M, K], w [N, K]");
-  SFT_CHECK(a.stride(1) == 1 && w.stride(1) == 1, "gemm_tn: K-contiguous operands");
-  SFT_CHECK(a.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, "gemm_tn: 16-byte aligned rows");
-  SFT_CHECK(a.size(0) % 256 == 0 && a.size(1) % tn::BK == 0 && a.size(1) > 0, "gemm_tn: M % 256, K % 32");
+  SFT_CHECK(a.dim() == 2 && w.dim() == 2 && a.size(1) == w.size(1), op, ": a [M, K], w [N, K]");
+  SFT_CHECK(a.stride(1) == 1 && w.stride(1) == 1, op, ": K-contiguous operands");
+  SFT_CHECK(a.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, op, ": 16-byte aligned rows");
+  SFT_CHECK(cfg == 5 || cfg == 11 || cfg == 60 || cfg == 61, op, ": cfg ", cfg, " not built (5, 11, 60, 61)");
+  const long M = a.size(0), N = w.size(0), K = a.size(1);
+  SFT_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K > 0, op, ": M % 256, N % 256, K % 64 (got M ", M,
+            ", N ", N, ", K ", K, ")");
 }
 
-// cfg: 0 = 256x256 BK32 ring (NS 5; any K % 32), 2 = 256x256 BK64 (NS 2), 5 = BK64 transposed-C epilogue, 11 = the
-// ping-pong 8-phase schedule (transposed-C, D = 2; the default for qkv + RoPE, with a 256 x 128 tail launch), 60 / 61 =
-// the persistent 4-wave kernel with the row-contiguous store epilogue (plain / nt stores: the plain forwards without a
-// TunableOp selection, the LoRA wide GEMM). Measurements: profiles/r1_gemm_tn.md, r2_gemm_pingpong.md,
-// r4_gemm_fwd.md, r5_gemm_fwd.md.
 at::Tensor gemm_tn(const at::Tensor& a, const at::Tensor& w, int64_t cfg) {
-  check_tn(a, w);
+  check_tn("gemm_tn", a, w, cfg);
   SFT_TRACE(trace_name("tn.c", cfg));
   const int M = a.size(0), N = w.size(0);
   auto c = at::empty({M, N}, a.options());
   tn::EpiArgs ea{(u16*)c.data_ptr(), nullptr, nullptr, nullptr, (long)N, 0, 0};
-  const bool k64 = a.size(1) % 64 == 0;
-  if (cfg == 2 || cfg == 5 || cfg == 11) {
-    SFT_CHECK(N % 256 == 0 && k64, "gemm_tn BK64: N % 256, K % 64");
-    if (cfg == 2) tn::launch2<256, 256, 2, 4, 2, tn::EPI_PLAIN>(a, w, N, ea);
-    else if (cfg == 5) tn::launch2<256, 256, 2, 4, 2, tn::EPI_PLAIN, 3>(a, w, N, ea);
-    else tn::launch3<tn::EPI_PLAIN, true, 2>(a, w, N, ea);
-  } else if (cfg == 60 || cfg == 61) {
-    tn::launch6<tn::EPI_PLAIN>(a, w, N, ea, cfg == 61);
-  } else {
-    SFT_CHECK(cfg == 0, "gemm_tn: cfg ", cfg, " not built (0, 2, 5, 11, 60, 61)");
-    SFT_CHECK(N % 256 == 0, "gemm_tn 256x256: N % 256");
-    tn::launch<256, 256, 2, 4, 5, tn::EPI_PLAIN>(a, w, N, ea);
-  }
+  tn::launch_cfg<tn::EPI_PLAIN>(cfg, a, w, N, ea);
   return c;
 }
 
 // x [M, K], w_gu [2I, K] = [gate; up]  ->  (gu [M, 2I], act [M, I] = silu(gate) * up)
 std::tuple<at::Tensor, at::Tensor> gemm_tn_swiglu(const at::Tensor& x, const at::Tensor& w_gu, int64_t cfg) {
-  check_tn(x, w_gu);
+  check_tn("gemm_tn_swiglu", x, w_gu, cfg);  // N % 256: the intermediate size is a multiple of 128
   SFT_TRACE(trace_name("tn.swiglu.c", cfg));
   const int M = x.size(0), N = w_gu.size(0), I = N / 2;
-  SFT_CHECK(N % 2 == 0 && I % 128 == 0, "gemm_tn_swiglu: intermediate size % 128");
   auto gu = at::empty({M, N}, x.options());
   auto act = at::empty({M, I}, x.options());
   tn::EpiArgs ea{(u16*)gu.data_ptr(), (u16*)act.data_ptr(), nullptr, nullptr, (long)N, I, 0};
-  SFT_CHECK(cfg == 0 || cfg == 2 || cfg == 5 || cfg == 11 || cfg == 60 || cfg == 61,
-            "gemm_tn_swiglu: cfg ", cfg, " not built (0, 2, 5, 11, 60, 61)");
-  if (cfg == 60 || cfg == 61) tn::launch6<tn::EPI_SWIGLU>(x, w_gu, N, ea, cfg == 61);
-  else if (x.size(1) % 64 == 0 && N % 256 == 0 && cfg == 11) tn::launch3<tn::EPI_SWIGLU, true, 2>(x, w_gu, N, ea);
-  else if (x.size(1) % 64 == 0) tn::launch2<256, 256, 2, 4, 2, tn::EPI_SWIGLU, 3>(x, w_gu, N, ea);
-  else tn::launch<256, 256, 2, 4, 5, tn::EPI_SWIGLU>(x, w_gu, N, ea);
+  tn::launch_cfg<tn::EPI_SWIGLU>(cfg, x, w_gu, N, ea);
   return {gu, act};
 }
 
@@ -1321,47 +1017,40 @@ std::tuple<at::Tensor, at::Tensor> gemm_tn_swiglu(const at::Tensor& x, const at:
 // applied to columns [0, rope_cols).
 at::Tensor gemm_tn_rope(const at::Tensor& x, const at::Tensor& w, const at::Tensor& cosb, const at::Tensor& sinb,
                         int64_t rope_cols, int64_t cfg) {
-  check_tn(x, w);
+  check_tn("gemm_tn_rope", x, w, cfg);
   SFT_TRACE(trace_name("tn.rope.c", cfg));
   const int M = x.size(0), N = w.size(0);
-  SFT_CHECK(N % 256 == 0 && rope_cols % 128 == 0, "gemm_tn_rope: N % 256, head_dim 128");
+  SFT_CHECK(rope_cols % 128 == 0, "gemm_tn_rope: head_dim 128 (got rope_cols ", rope_cols, ")");
   SFT_CHECK(cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
                 sinb.is_contiguous() && cosb.numel() == (long)M * 64 && sinb.numel() == (long)M * 64,
             "gemm_tn_rope: cos/sin [M, 64] fp32");
   auto c = at::empty({M, N}, x.options());
   tn::EpiArgs ea{(u16*)c.data_ptr(), nullptr, cosb.data_ptr<float>(), sinb.data_ptr<float>(), (long)N, 0,
                  (int)rope_cols};
-  SFT_CHECK(cfg == 0 || cfg == 2 || cfg == 5 || cfg == 11 || cfg == 60 || cfg == 61,
-            "gemm_tn_rope: cfg ", cfg, " not built (0, 2, 5, 11, 60, 61)");
-  if (cfg == 60 || cfg == 61) tn::launch6<tn::EPI_ROPE>(x, w, N, ea, cfg == 61);
-  else if (cfg == 2 && x.size(1) % 64 == 0) tn::launch2<256, 256, 2, 4, 2, tn::EPI_ROPE>(x, w, N, ea);
-  else if (cfg == 5 && x.size(1) % 64 == 0) tn::launch2<256, 256, 2, 4, 2, tn::EPI_ROPE, 3>(x, w, N, ea);
-  else if (cfg == 11 && x.size(1) % 64 == 0) {
-    // Wave-quantisation tail (gemm_dgrad.hip does the same): the SmolLM3 qkv grid is 32 x 12 = 384 tiles of
-    // 256 x 256 = 1.5 rounds of 256 CUs. The whole round runs as one launch over the leading columns and the
-    // leftover columns as 256 x 128 tiles (one round at about half a tile's time) in a second launch; heads never
-    // straddle the cut (a multiple of 256), the tail's rope boundary is shifted with its pointers.
-    // SFTAMD_TN_TAIL=0: one launch.
-    const char* e = std::getenv("SFTAMD_TN_TAIL");
-    const bool tail_on = !(e && e[0] == '0');
-    const int nbm = M / 256, nbn = N / 256, tiles = nbm * nbn;
-    int main_n = 0;
-    if (tail_on && tiles % 256 != 0 && 256 % nbm == 0) {
-      main_n = tiles / 256 * (256 / nbm);
-      if ((nbn - main_n) * 2 * nbm > 256) main_n = 0;  // the 256 x 128 tail must fit one round
-    }
-    if (main_n <= 0) {
-      tn::launch3<tn::EPI_ROPE, true, 2>(x, w, N, ea);
-    } else {
-      const int ncut = main_n * 256;
-      SFT_TRACE("tn.rope.tail");
-      tn::launch3<tn::EPI_ROPE, true, 2>(x, w.narrow(0, 0, ncut), ncut, ea);
-      tn::EpiArgs et = ea;
-      et.C = ea.C + ncut;
-      et.rope_cols = std::max(0, ea.rope_cols - ncut);
-      tn::launch2<256, 128, 4, 2, 3, tn::EPI_ROPE>(x, w.narrow(0, ncut, N - ncut), N - ncut, et);
-    }
-  } else tn::launch<256, 256, 2, 4, 5, tn::EPI_ROPE>(x, w, N, ea);
+  // cfg 11, wave-quantisation tail (gemm_dgrad.hip does the same): the SmolLM3 qkv grid is 32 x 12 = 384 tiles of
+  // 256 x 256 = 1.5 rounds of 256 CUs. The whole round runs as one launch over the leading columns and the
+  // leftover columns as 256 x 128 tiles (one round at about half a tile's time) in a second launch; heads never
+  // straddle the cut (a multiple of 256), the tail's rope boundary is shifted with its pointers.
+  // SFTAMD_TN_TAIL=0: one launch.
+  const char* e = std::getenv("SFTAMD_TN_TAIL");
+  const bool tail_on = !(e && e[0] == '0');
+  const int nbm = M / 256, nbn = N / 256, tiles = nbm * nbn;
+  int main_n = 0;
+  if (cfg == 11 && tail_on && tiles % 256 != 0 && 256 % nbm == 0) {
+    main_n = tiles / 256 * (256 / nbm);
+    if ((nbn - main_n) * 2 * nbm > 256) main_n = 0;  // the 256 x 128 tail must fit one round
+  }
+  if (main_n <= 0) {
+    tn::launch_cfg<tn::EPI_ROPE>(cfg, x, w, N, ea);
+  } else {
+    const int ncut = main_n * 256;
+    SFT_TRACE("tn.rope.tail");
+    tn::launch3<tn::EPI_ROPE>(x, w.narrow(0, 0, ncut), ncut, ea);
+    tn::EpiArgs et = ea;
+    et.C = ea.C + ncut;
+    et.rope_cols = std::max(0, ea.rope_cols - ncut);
+    tn::launch2<256, 128, 4, 2, 3, tn::EPI_ROPE, false>(x, w.narrow(0, ncut, N - ncut), N - ncut, et);
+  }
   return c;
 }
 

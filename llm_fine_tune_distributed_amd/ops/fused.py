@@ -444,7 +444,17 @@ def _as_output(y2d: torch.Tensor, lead) -> torch.Tensor:
 # where hipBLASLt's default heuristics pick split-K kernels that took 36 % of the recipe's kernel time
 # (profiles/r5_recipe.md). SFTAMD_FWD_GEMM: auto (this rule) | blas | hip.
 _FWD_GEMM = os.environ.get("SFTAMD_FWD_GEMM", "auto")
-_ROWC_CFG = int(os.environ.get("SFTAMD_TN_CFG", "60"))  # row-contiguous persistent kernel (60: cacheable stores)
+
+
+def _rowc_cfg_env(var: str, default: str) -> int:
+    """A row-contiguous persistent kernel config from the environment: 60 (cacheable stores) or 61 (nt stores)."""
+    val = os.environ.get(var, default)
+    if val not in ("60", "61"):
+        raise ValueError(f"{var}={val!r}: the persistent forward GEMM is built as cfg 60 or 61 only")
+    return int(val)
+
+
+_ROWC_CFG = _rowc_cfg_env("SFTAMD_TN_CFG", "60")  # 60: cacheable stores
 
 
 def _rowc_ok(x2d: torch.Tensor, w: torch.Tensor) -> bool:
@@ -918,7 +928,9 @@ _TN_MODE = os.environ.get("SFTAMD_TN", "rope")  # rope | swiglu | 1 (both) | 0 (
 
 
 def _tn_ok(x2d: torch.Tensor, w: torch.Tensor) -> bool:
-    """Shapes the forward-layout HIP GEMM (csrc/gemm_tn.hip, BK64 tiles of 256 x 256) handles.
+    """Shapes the epilogue-fused forward GEMMs (csrc/gemm_tn.hip: gemm_tn_rope, gemm_tn_swiglu) handle: whole
+    256 x 256 output tiles and 64-deep K-tiles (the ping-pong kernel, cfg 11; the persistent kernel the SwiGLU
+    projection prefers needs K % 128 == 0 on top, _tn_swiglu_cfg).
 
     Default (measured end to end on MI355X, profiles/r1_gemm_tn.md): the qkv projection runs with the
     RoPE epilogue (beats hipBLASLt + the rope kernel); gate_up + SwiGLU stays on hipBLASLt + the SwiGLU
@@ -927,16 +939,6 @@ def _tn_ok(x2d: torch.Tensor, w: torch.Tensor) -> bool:
     return (_TN_MODE != "0" and _ext.use_hip(x2d) and x2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
             and x2d.dim() == 2 and x2d.shape[0] % 256 == 0 and x2d.shape[0] > 0 and x2d.shape[1] % 64 == 0
             and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and w.is_contiguous() and w.shape[0] % 256 == 0)
-
-
-def _tn_cfg() -> int:
-    """Forward GEMM with an epilogue (qkv + RoPE; every caller requires N % 256 == 0): the ping-pong 8-phase schedule
-    (cfg 11, csrc/gemm_tn.hip: the two wave rows one barrier apart, transposed-C epilogue) — 2-6 % faster than the
-    BK64 ring (cfg 2) on every SmolLM3 shape (profiles/r2_gemm_pingpong.md). The persistent row-contiguous kernel
-    (cfg 61) is faster in isolation (0.121 vs 0.131 ms) but slower in the step: 137 vs 106 us per call, its 384 tiles
-    are 1.5 rounds of one workgroup per CU and the cos / sin loads of its epilogue wait behind the next tile's DMA
-    (profiles/r5_gemm_fwd.md)."""
-    return 11
 
 
 class GateUpSwiGLUFn(Function):
@@ -1030,7 +1032,7 @@ class QKVRopeFn(Function):
     @staticmethod
     def forward(ctx, x, weight, cos, sin, n_q, n_kv, head_dim):
         x2d = x.reshape(-1, x.shape[-1])
-        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
+        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim)
         ctx.save_for_backward(x2d, cos, sin)
         ctx.weight = weight
         ctx.dims = (n_q, n_kv, head_dim)
@@ -1057,6 +1059,12 @@ def _rope_epilogue_ok(x2d, weight, cos, sin, head_dim) -> bool:
 
 def linear_rope(x, weight, cos, sin, n_q, n_kv, head_dim):
     """rope_(linear(x, W_qkv)) on the packed [M, (n_q + 2 n_kv) * head_dim] layout."""
+    # gemm_tn_rope runs at its default cfg 11, the ping-pong 8-phase schedule (csrc/gemm_tn.hip: the two wave rows one
+    # barrier apart, transposed-C epilogue): 2-6 % faster than the BK64 ring (the former cfg 2) on every SmolLM3 shape
+    # (profiles/r2_gemm_pingpong.md). The persistent row-contiguous kernel (cfg 61) with a RoPE epilogue was faster in
+    # isolation (0.121 vs 0.131 ms) but slower in the step: 137 vs 106 us per call, its 384 tiles are 1.5 rounds of
+    # one workgroup per CU and the cos / sin loads of its epilogue wait behind the next tile's DMA
+    # (profiles/r5_gemm_fwd.md).
     x2d = x.reshape(-1, x.shape[-1])
     if _TN_MODE in ("1", "rope") and _tn_ok(x2d, weight) and _rope_epilogue_ok(x2d, weight, cos, sin, head_dim):
         return QKVRopeFn.apply(x, weight, cos, sin, n_q, n_kv, head_dim)
@@ -1270,7 +1278,7 @@ class QKVRopeAttnFn(Function):
             if _WGRAD_PAIR and weight.requires_grad:  # this node's backward runs: o_proj may leave its wgrad here
                 link.qkv_takes_o_wgrad = True
         x2d = x.reshape(-1, x.shape[-1])
-        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
+        qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim)
         out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
         ctx.save_for_backward(x2d, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.weight = weight
@@ -1680,7 +1688,7 @@ def _lora_gemm(X: torch.Tensor, wide: torch.Tensor) -> torch.Tensor:
 
 # the persistent 4-wave kernel with the row-contiguous nt store epilogue (csrc/gemm_tn.hip cfg 61): 131.3 vs 130.2
 # samples/s for cfg 164 (r5_run08, one box)
-_LORA_FWD_CFG = int(os.environ.get("SFTAMD_LORA_FWD_CFG", "61"))
+_LORA_FWD_CFG = _rowc_cfg_env("SFTAMD_LORA_FWD_CFG", "61")
 
 
 def _lora_wide_prep(x, wide, K, scaling, p, seed, meta, ab, swiglu=False):
@@ -1848,7 +1856,7 @@ class LoRAQKVRopeAttnFn(Function):
     def forward(ctx, x, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, wide, K, scaling, p,
                 seed, meta, *ab):
         X, acat, state = _lora_wide_prep(x, wide, K, scaling, p, seed, meta, ab)
-        qkv = _ext.ops().gemm_tn_rope(X, wide, cos, sin, (n_q + n_kv) * head_dim, _tn_cfg())
+        qkv = _ext.ops().gemm_tn_rope(X, wide, cos, sin, (n_q + n_kv) * head_dim)
         out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
         ctx.save_for_backward(X, acat, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.wide, ctx.adapters, ctx.meta = wide, ab, state

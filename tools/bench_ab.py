@@ -6,7 +6,7 @@ error against the first variant.
     python tools/bench_ab.py dgrad gate_up 14,15,16
     python tools/bench_ab.py wgrad lm_head 10,1214 --rounds 5
 
-wgrad: dW[N, K] = dy[T, N]^T x[T, K] (sftamd.wgrad_gemm cfg); fwd: y[T, N] = x[T, K] W[N, K]^T (sftamd.gemm_tn cfg); dgrad: dX[T, N] = dy[T, K] W[K, N] (sftamd.dgrad_gemm cfg;
+wgrad: dW[N, K] = dy[T, N]^T x[T, K] (sftamd.wgrad_gemm cfg); fwd: y[T, N] = x[T, K] W[N, K]^T (sftamd.gemm_tn cfg 5 | 11 | 60 | 61); dgrad: dX[T, N] = dy[T, K] W[K, N] (sftamd.dgrad_gemm cfg;
 'blas' = torch.mm on the TunableOp selection; 'delta' = dgrad_gemm_delta). SmolLM3-3B shapes at T = 8192 tokens;
 Llama-3-8B ones as l8b_qkv, l8b_o, l8b_gate_up, l8b_down, l8b_lm_head.
 """

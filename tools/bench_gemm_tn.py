@@ -19,10 +19,10 @@ from llm_fine_tune_distributed_amd.utils.gemm_tuning import enable_tuned_gemms  
 ap = argparse.ArgumentParser()
 ap.add_argument("--m", type=int, default=8192)
 ap.add_argument("--iters", type=int, default=20)
-ap.add_argument("--cfgs", default="0,2,5,11,60,61", help="gemm_tn configurations to time")
+ap.add_argument("--cfgs", default="5,11,60,61", help="gemm_tn configurations to time (5, 11, 60, 61)")
 ap.add_argument("--shapes", default="", help="name:N:K,... instead of the SmolLM3 projection shapes")
 ap.add_argument("--plain-only", action="store_true", help="skip the fused-epilogue section")
-ap.add_argument("--fused-cfgs", default="", help="time only gemm_tn_swiglu / gemm_tn_rope at these cfgs vs their unfused "
+ap.add_argument("--fused-cfgs", default="", help="time only gemm_tn_swiglu / gemm_tn_rope at these cfgs (5, 11, 60, 61) vs their unfused "
                                                   "twins (skips the plain table)")
 a = ap.parse_args()
 assert _ext.load(), _ext.load_error()
@@ -115,10 +115,10 @@ x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
 wgu = torch.randn(2 * I, K, device="cuda", dtype=torch.bfloat16) * 0.02
 gu_ref = torch.nn.functional.linear(x, wgu)
 act_ref = ops.swiglu_fwd(gu_ref)
-gu, act = ops.gemm_tn_swiglu(x, wgu)
+gu, act = ops.gemm_tn_swiglu(x, wgu, 60)
 print(f"\nswiglu fused: gu rel err {rel(gu, gu_ref):.4f}, act rel err {rel(act, act_ref):.4f}")
 t0 = timeit(lambda: ops.swiglu_fwd(torch.nn.functional.linear(x, wgu)))
-t1 = timeit(lambda: ops.gemm_tn_swiglu(x, wgu))
+t1 = timeit(lambda: ops.gemm_tn_swiglu(x, wgu, 60))
 print(f"gate_up + SwiGLU: blas + kernel {t0:.3f} ms, fused {t1:.3f} ms ({(t0 - t1) * 1e3:.0f} us saved per layer)")
 
 nq, nkv, D = 16, 4, 128
@@ -138,7 +138,7 @@ def unfused():
 qr = unfused()
 t0 = timeit(unfused)
 parts = [f"blas + kernel {t0:.3f} ms"]
-for cfg in (0, 2, 5, 11, 60, 61):
+for cfg in (5, 11, 60, 61):
     qf = ops.gemm_tn_rope(x, wq, cs, sn, (nq + nkv) * D, cfg)
     t = timeit(lambda: ops.gemm_tn_rope(x, wq, cs, sn, (nq + nkv) * D, cfg))
     parts.append(f"cfg{cfg} {t:.3f} ms (rel err {rel(qf, qr):.4f})")

@@ -35,7 +35,8 @@ def attn_ok():
 
 
 def tn_ok():
-    # csrc/gemm_tn.hip BK32: 64-B rows, chunk ^ S((row >> 2) & 3); BK64: 128-B rows, chunk ^ ((row >> 1) & 7)
+    # csrc/gemm_dgrad.hip dY image (swz64): 64-B rows, chunk ^ S((row >> 2) & 3);
+    # csrc/gemm_tn.hip and gemm_dgrad.hip BK64 (swz128): 128-B rows, chunk ^ ((row >> 1) & 7)
     for R in (0, 16, 32):
         for grp in B128_GROUPS:
             slots = {((R + (l & 15)) * 64 % 256) // 16 + ((l >> 4) ^ S[((R + (l & 15)) >> 2) & 3]) for l in grp}

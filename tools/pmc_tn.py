@@ -1,4 +1,4 @@
-"""One forward-layout GEMM variant for PMC passes: rocprofv3 --pmc ... -- python tools/pmc_tn.py <cfg|blas> [N K]."""
+"""One forward-layout GEMM variant for PMC passes: rocprofv3 --pmc ... -- python tools/pmc_tn.py <5|11|60|61|blas> [N K]."""
 import os
 import sys
 
