@@ -263,10 +263,14 @@ __device__ __forceinline__ void store_t21(u16* row, const f32x16 (&a)[4], float 
 // One 64-key tile: issue the next tile's K / V pieces into nxt (4 x 1 KB per image per wave, source-swizzled, rows
 // past the sequence end clamped: their keys are masked), then S^T, the online softmax and O^T += V^T P^T from cur.
 // lastkey: the wave's last visible key (causal: its last query); rel: this lane's last visible key - k0 - 4 hi.
+// WIN (sliding window): firstkey is the wave's first visible key (its first query's), rello this lane's first visible
+// key - k0 - 4 hi. A row whose keys of this tile are all below its window keeps m = -1e30 and adds exp2(-inf) = 0.
+template <bool WIN>
 __device__ __forceinline__ void fwd32_step(const char* __restrict__ cur, char* __restrict__ nxt, bool pre, rsrc_t kv,
                                            unsigned voffk, unsigned voffv, unsigned rowb, int wave, int k0, int lastkey,
                                            bool need_mask, int rel, float sl2, const Offs32& off,
-                                           const bf16x8 (&qf)[8], f32x16 (&o)[4], float& m, float& l) {
+                                           const bf16x8 (&qf)[8], f32x16 (&o)[4], float& m, float& l,
+                                           int firstkey = 0, int rello = 0) {
   constexpr int TB = 64 * ROWB;
   if (pre) {
 #pragma unroll
@@ -277,6 +281,7 @@ __device__ __forceinline__ void fwd32_step(const char* __restrict__ cur, char* _
     }
   }
   if (k0 > lastkey) return;
+  if (WIN && k0 + 63 < firstkey) return;  // (wave-uniform) every key of the tile is below the wave's windows
   const bool two = k0 + 32 <= lastkey;  // wave-uniform: the second 32-key half has a visible key
   const char* Ks = cur;
   const char* Vs = cur + TB;
@@ -297,7 +302,12 @@ __device__ __forceinline__ void fwd32_step(const char* __restrict__ cur, char* _
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        s[kb][i] = 32 * kb + (i & 3) + 8 * (i >> 2) > rel ? -INFINITY : s[kb][i];
+        if (WIN) {
+          const int kk = 32 * kb + (i & 3) + 8 * (i >> 2);
+          s[kb][i] = (kk > rel || kk < rello) ? -INFINITY : s[kb][i];
+        } else {
+          s[kb][i] = 32 * kb + (i & 3) + 8 * (i >> 2) > rel ? -INFINITY : s[kb][i];
+        }
   }
   float mx = max3f(s[0][0], s[0][1], s[0][2]);
 #pragma unroll
@@ -339,11 +349,16 @@ __device__ __forceinline__ void fwd32_step(const char* __restrict__ cur, char* _
 }
 
 // grid (nq / HW, sequences, position blocks of 32 (4 / HW)) with the last (causally heaviest) block first; 256 threads
-template <int HW>
+// WIN: causal sliding window, query i sees keys (i - window, i]. The key-tile loop (and the first prefetch) starts at
+// the tile of the workgroup's first visible key; tiles that straddle a row's lower edge take the mask. The kernel's
+// arguments are the same either way (so the plain instantiations are the code they were): with WIN, causal holds
+// the window.
+template <int HW, bool WIN>
 __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ qkv, u16* __restrict__ out,
                                                        float* __restrict__ lse, const int* __restrict__ cu, int nq,
                                                        int nkv, int total, float sl2, int causal) {
   constexpr int PB = 4 / HW, TB = 64 * ROWB;
+  const int window = WIN ? causal : 0;  // (the WIN instantiations get the window in causal: it implies the mask)
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
   const int b = blockIdx.y, qb = gridDim.z - 1 - blockIdx.z;
   const int start = cu[b], len = cu[b + 1] - start;
@@ -361,6 +376,7 @@ __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ q
   const int nkt = causal ? min((min(q0 + 32 * PB, len) - 1) / 64 + 1, nkb) : nkb;
   const int lastkey = causal ? min(wq0 + 31, len - 1) : len - 1;
   const int lim = causal ? min(len - 1, qi) : len - 1;
+  const int kt0 = WIN ? max(q0 - window + 1, 0) / 64 : 0;
   Offs32 off;
   off.init(lane);
   const unsigned rowb = (unsigned)ld * 2;
@@ -378,8 +394,8 @@ __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ q
   const unsigned voffk = (unsigned)r0 * rowb + 16 * swz(r0, lane & 15), voffv = voffk + nkv * ROWB;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    bldsx4(kv, smem + (wave + 4 * j) * 1024, voffk, 16 * j * rowb);
-    bldsx4(kv, smem + TB + (wave + 4 * j) * 1024, voffv, 16 * j * rowb);
+    bldsx4(kv, smem + (kt0 & 1) * 2 * TB + (wave + 4 * j) * 1024, voffk, (kt0 * 64 + 16 * j) * rowb);
+    bldsx4(kv, smem + (kt0 & 1) * 2 * TB + TB + (wave + 4 * j) * 1024, voffv, (kt0 * 64 + 16 * j) * rowb);
   }
   vm_drain();
   f32x16 o[4];
@@ -389,12 +405,14 @@ __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ q
     for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
   float m = -1e30f, l = 0.f;  // l: this lane's partial row sum (its 16 keys of each 32-key block)
   __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
+  for (int kt = kt0; kt < nkt; ++kt) {
     const int k0 = kt * 64;
     const bool pre = kt + 1 < nkt;
-    const bool need_mask = (k0 + 64 > len) || (causal && k0 + 63 > wq0);
-    fwd32_step(smem + (kt & 1) * 2 * TB, smem + ((kt + 1) & 1) * 2 * TB, pre, kv, voffk, voffv, rowb, wave, k0,
-               lastkey, need_mask, lim - k0 - 4 * hi, sl2, off, qf, o, m, l);
+    // (WIN: + the lower edge, a key of the tile below the window of the wave's last query)
+    const bool need_mask = (k0 + 64 > len) || (causal && k0 + 63 > wq0) || (WIN && k0 < wq0 + 32 - window);
+    fwd32_step<WIN>(smem + (kt & 1) * 2 * TB, smem + ((kt + 1) & 1) * 2 * TB, pre, kv, voffk, voffv, rowb, wave, k0,
+                    lastkey, need_mask, lim - k0 - 4 * hi, sl2, off, qf, o, m, l, WIN ? wq0 - window + 1 : 0,
+                    WIN ? qi - window + 1 - k0 - 4 * hi : 0);
     if (pre) vm_drain();
     __syncthreads();
   }
@@ -406,13 +424,15 @@ __global__ __launch_bounds__(256, 2) void fwd32_kernel(const u16* __restrict__ q
 
 // dQ past the dS^T budget (long contexts): per 64-key tile S^T and dP^T are recomputed from Q, K, V, dO, lse and delta
 // (16x16x32 MFMAs, 48 per tile and wave instead of dq32's 16) and dQ^T += K^T dS^T; 8 waves x 16 queries.
-template <int NW>
+// WIN: the key tiles start at the block's first visible key, as in fwd32; the mask gains the window's lower edge.
+template <int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict__ qkv, const u16* __restrict__ dout,
                                                           const float* __restrict__ lse,
                                                           const float* __restrict__ delta, const int* __restrict__ cu,
                                                           u16* __restrict__ dqkv, int nq, int nkv, int total,
                                                           float sl2, float scale, int causal) {
   constexpr int NT = NW * 64, BM = NW * 16, TB = 64 * ROWB;
+  const int window = WIN ? causal : 0;  // (the WIN instantiations get the window in causal: it implies the mask)
   __shared__ __attribute__((aligned(16))) char smem[2 * TB];
   char* Ks = smem;
   char* Vs = smem + TB;
@@ -433,12 +453,13 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
   const u16* vbase = qkv + (long)start * ld + (nq + nkv + kvh) * D;
   const int nkb = (len + 63) / 64;
   const int nkt = causal ? min((q0 + BM + 63) / 64, nkb) : nkb;
+  const int kt0 = WIN ? max(q0 - window + 1, 0) / 64 : 0;
   Offs off;
   off.init(lane);
   {
     Stage<64, NT> tk, tv;
-    tk.load(kbase, ld, len, tid);
-    tv.load(vbase, ld, len, tid);
+    tk.load(kbase + (long)kt0 * 64 * ld, ld, len - kt0 * 64, tid);
+    tv.load(vbase + (long)kt0 * 64 * ld, ld, len - kt0 * 64, tid);
     tk.store(Ks, tid);
     tv.store(Vs, tid);
   }
@@ -458,7 +479,7 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
+  for (int kt = kt0; kt < nkt; ++kt) {
     const int k0 = kt * 64;
     const bool pre = kt + 1 < nkt;
     Stage<64, NT> tk, tv;
@@ -466,7 +487,7 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
       tk.load(kbase + (long)(k0 + 64) * ld, ld, len - k0 - 64, tid);
       tv.load(vbase + (long)(k0 + 64) * ld, ld, len - k0 - 64, tid);
     }
-    if (!causal || k0 <= wfirst + 15) {
+    if ((!causal || k0 <= wfirst + 15) && (!WIN || k0 + 63 > wfirst - window)) {
       f32x4 sc[4], dp[4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
@@ -478,7 +499,8 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
           dp[nt] = mfma(lds_row(Vs, off.row[s] + nt * 16 * ROWB), df[s], dp[nt]);
         }
       }
-      const bool need_mask = (k0 + 64 > len) || (causal && k0 + 63 > wfirst) || (q0 + BM > len);
+      const bool need_mask = (k0 + 64 > len) || (causal && k0 + 63 > wfirst) || (q0 + BM > len) ||
+                             (WIN && k0 < wfirst + 16 - window);
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -486,7 +508,7 @@ __global__ __launch_bounds__(NW * 64) void bwd_dq3_kernel(const u16* __restrict_
           float p = exp2f(fmaf(sc[nt][i], sl2, -lse2));
           if (need_mask) {
             const int key = k0 + 16 * nt + 4 * g + i;
-            if (key >= len || (causal && key > qrow) || !qok) p = 0.f;
+            if (key >= len || (causal && key > qrow) || !qok || (WIN && key <= qrow - window)) p = 0.f;
           }
           dp[nt][i] = p * (dp[nt][i] - dl);
         }
@@ -562,13 +584,17 @@ __device__ __forceinline__ void dq32_step(const char* __restrict__ cur, char* __
   }
 }
 
-template <int HW>
+// WIN: the key tiles start at the workgroup's first visible key (fwd32's bound) and a wave reads a tile only if its
+// first query sees one of the tile's keys — exactly the (key tile, query tile) blocks bwd_dkdv32<WIN> wrote: its key
+// block kb covers the query tiles up to that of query 64 kb + 62 + window, and it stores masked elements as zeros.
+template <int HW, bool WIN>
 __global__ __launch_bounds__(256, 2) void bwd_dq32_kernel(const u16* __restrict__ qkv, const u16* __restrict__ dst,
                                                           const int* __restrict__ cu, u16* __restrict__ dqkv, int nq,
                                                           int nkv, int lp, float scale, int causal,
                                                           const float* __restrict__ rcos,
                                                           const float* __restrict__ rsin) {
   constexpr int PB = 4 / HW, TB = 64 * ROWB, SB = 64 * 64, STG = TB + 4 * SB;
+  const int window = WIN ? causal : 0;  // (the WIN instantiations get the window in causal: it implies the mask)
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
   const int b = blockIdx.y, qb = gridDim.z - 1 - blockIdx.z;
   const int start = cu[b], len = cu[b + 1] - start;
@@ -586,6 +612,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq32_kernel(const u16* __restrict_
   const u16* sbase = dst + (long)(b * nq + h) * lp * lp + wq0;
   const int nkb = (len + 63) / 64;
   const int nkt = causal ? min((min(q0 + 32 * PB, len) - 1) / 64 + 1, nkb) : nkb;
+  const int kt0 = WIN ? max(q0 - window + 1, 0) / 64 : 0;
   Offs32 off;
   off.init(lane);
   // this lane's dS^T transposed read: group a = lane >> 4 reads rows 4 hi + q (+ 8) of a 16-key step, columns
@@ -602,13 +629,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dq32_kernel(const u16* __restrict_
   for (int d4 = 0; d4 < 4; ++d4)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[d4][i] = 0.f;
-  dq32_step(smem + STG, smem, true, false, kr, sr, voffk, voffs, rowb, rows, 0, wave, off, sofs, dq);
+  dq32_step(smem + ((kt0 + 1) & 1) * STG, smem + (kt0 & 1) * STG, true, false, kr, sr, voffk, voffs, rowb, rows,
+            kt0 * 64, wave, off, sofs, dq);
   vm_drain();
   __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
+  for (int kt = kt0; kt < nkt; ++kt) {
     const int k0 = kt * 64;
     const bool pre = kt + 1 < nkt;
-    dq32_step(smem + (kt & 1) * STG, smem + ((kt + 1) & 1) * STG, pre, !causal || k0 <= lastq, kr, sr, voffk, voffs,
+    dq32_step(smem + (kt & 1) * STG, smem + ((kt + 1) & 1) * STG, pre,
+              WIN ? (k0 <= lastq && k0 + 63 > wq0 - window) : (!causal || k0 <= lastq), kr, sr, voffk, voffs,
               rowb, rows, k0 + 64, wave, off, sofs, dq);
     if (pre) vm_drain();  // this lane's pieces of the next tile landed ...
     __syncthreads();      // ... and every lane's (LDS zero stores too); every wave is done reading this stage
@@ -634,13 +663,14 @@ __global__ __launch_bounds__(256, 2) void bwd_dq32_kernel(const u16* __restrict_
 // queries x 4 products), 32 ds_read_b128 + 64 ds_read_b64_tr_b16 — half the LDS bytes per FLOP of the 16x16x32
 // dK/dV kernel it replaced. dS^T ([b][h][key][q], row stride lp) is written for bwd_dq32 when drow is given
 // (T21-paired 16-B stores).
+template <bool WIN>
 __device__ __forceinline__ void dkdv32_step(const char* __restrict__ cur, char* __restrict__ nxt, bool pre,
                                             rsrc_t qr, rsrc_t orr, unsigned vq0, unsigned vq1, unsigned vo0,
                                             unsigned vo1, unsigned qso, unsigned oso, unsigned rowb, unsigned rowo,
                                             int wv, const float* lsrc, const float* dsrc, int gl, int q0, int len,
                                             int causal, int kw0, int key, float sl2, u16* drow,
                                             const Offs32& off, const bf16x8 (&kf)[8], const char* Vk,
-                                            f32x16 (&dk)[4], f32x16 (&dv)[4]) {
+                                            f32x16 (&dk)[4], f32x16 (&dv)[4], int window) {
   constexpr int TB = 64 * ROWB;
   float pl = 0.f, pd = 0.f;
   if (pre) {  // the next tile (rows from qso / oso): image rows 4 (wv + 2 j) + (lane >> 4); rows past the sequence
@@ -673,8 +703,11 @@ __device__ __forceinline__ void dkdv32_step(const char* __restrict__ cur, char* 
     }
     // query q = q0 + 32 qb + 4 hi + o, o = 8 m + t for register 4 m + t; visible iff lo <= o <= hq
     const int qbase = q0 + 32 * qb + 4 * hi;
-    const int lo = (causal ? key : 0) - qbase, hq = len - 1 - qbase;
-    const bool need_mask = (q0 + 32 * qb + 31 >= len) || (causal && kw0 + 31 > q0 + 32 * qb);
+    // (WIN: the key's last query is key + window - 1: the upper edge of the window, in the same compare)
+    const int lo = (causal ? key : 0) - qbase, hq = (WIN ? min(len, key + window) : len) - 1 - qbase;
+    const bool need_mask =
+        WIN ? (q0 + 32 * qb + 31 >= len) || (kw0 + 31 > q0 + 32 * qb) || (q0 + 32 * qb + 31 >= kw0 + window)
+            : (q0 + 32 * qb + 31 >= len) || (causal && kw0 + 31 > q0 + 32 * qb);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const float4 L4 = *(const float4*)(Ls + 32 * qb + 8 * m + 4 * hi);
@@ -728,12 +761,15 @@ __device__ __forceinline__ void dkdv32_step(const char* __restrict__ cur, char* 
   }
 }
 
-template <int G>
+// WIN: the query tiles of key block kb end at the tile of query k0 + 62 + window, the last one that sees a key of the
+// block (nqt below: niter, the (h, qt) wrap-around and the lse / delta prefetch all follow it).
+template <int G, bool WIN>
 __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
     const u16* __restrict__ qkv, const u16* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, const int* __restrict__ cu, u16* __restrict__ dqkv, int nq, int nkv, int total,
     float sl2, float scale, int causal, u16* __restrict__ dst, int lp, const float* __restrict__ rcos,
     const float* __restrict__ rsin) {
+  const int window = WIN ? causal : 0;  // (the WIN instantiations get the window in causal: it implies the mask)
   constexpr int TB = 64 * ROWB, GB = 2 * TB + 2 * 64 * 4;  // per stage: Q, dO images + lse, delta
   __shared__ __attribute__((aligned(16))) char smem[G * 2 * GB + TB];  // + the workgroup's V image (64 keys)
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), grp = w >> 1, kh = w & 1;
@@ -750,7 +786,9 @@ __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
   const long ldo = (long)nq * D;
   const int kw0 = k0 + 32 * kh, key = kw0 + (lane & 31);
   const bool kok = key < len;
-  const int qt0 = causal ? kb : 0, nqt = (len + 63) / 64, nt = nqt - qt0, niter = hpg * nt;
+  const int qt0 = causal ? kb : 0;
+  const int nqt = WIN ? min((len + 63) / 64, (k0 + 62 + window) / 64 + 1) : (len + 63) / 64;
+  const int nt = nqt - qt0, niter = hpg * nt;
   Offs32 off;
   off.init(lane);
   int h = kvh * rep + grp * hpg, qt = qt0;
@@ -815,10 +853,10 @@ __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
     const long lo = (long)hn * total + start + qn;
     const bool lok = pre && qn + gl < len;
     u16* drow = dst != nullptr ? dst + ((long)(b * nq + h) * lp + key) * lp + q0 : nullptr;
-    dkdv32_step(base + (it & 1) * GB, base + ((it + 1) & 1) * GB, pre, qr, orr, vq0, vq1, vo0, vo1,
+    dkdv32_step<WIN>(base + (it & 1) * GB, base + ((it + 1) & 1) * GB, pre, qr, orr, vq0, vq1, vo0, vo1,
                 (unsigned)qn * rowb + hn * ROWB, (unsigned)qn * rowo + hn * ROWB, rowb, rowo, kh,
                 lok ? lse + lo : nullptr, delta + lo, gl, q0, len, causal, kw0, key, sl2, drow, off, kf, Vk, dk,
-                dv);
+                dv, window);
     if (pre) vm_drain();  // this lane's pieces of the next tile landed ...
     __syncthreads();      // ... and every lane's; every wave is done reading this stage
     h = hn;
@@ -868,15 +906,21 @@ __global__ __launch_bounds__(128 * G, 1) void bwd_dkdv32_kernel(
 // host launcher of the GQA-grouped dK/dV: G = 2 head groups when rep is even, else G = 1
 static void launch_dkdv(const u16* qkv, const u16* dout, const float* lse, const float* delta, const int* cu,
                         u16* dqkv, int nq, int nkv, int total, int nseq, int max_seqlen, float sl2, float scale,
-                        int causal, u16* dst, int lp, hipStream_t st, const float* rcos = nullptr,
+                        int causal, u16* dst, int lp, hipStream_t st, int window, const float* rcos = nullptr,
                         const float* rsin = nullptr) {
   dim3 grid(nkv, nseq, (max_seqlen + 63) / 64);
-  if ((nq / nkv) % 2 == 0)
-    bwd_dkdv32_kernel<2><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, cu, dqkv, nq, nkv, total, sl2, scale, causal,
-                                               dst, lp, rcos, rsin);
-  else
-    bwd_dkdv32_kernel<1><<<grid, 128, 0, st>>>(qkv, dout, lse, delta, cu, dqkv, nq, nkv, total, sl2, scale, causal,
-                                               dst, lp, rcos, rsin);
+  const bool g2 = (nq / nkv) % 2 == 0;
+#define SFT_DKDV(G, WIN)                                                                                            \
+  bwd_dkdv32_kernel<G, WIN><<<grid, 128 * G, 0, st>>>(qkv, dout, lse, delta, cu, dqkv, nq, nkv, total, sl2, scale, \
+                                                      WIN ? window : causal, dst, lp, rcos, rsin)
+  if (window > 0) {
+    if (g2) SFT_DKDV(2, true);
+    else SFT_DKDV(1, true);
+  } else {
+    if (g2) SFT_DKDV(2, false);
+    else SFT_DKDV(1, false);
+  }
+#undef SFT_DKDV
 }
 
 }  // namespace attn
@@ -891,6 +935,14 @@ static void check_attn_args(const at::Tensor& qkv, const at::Tensor& cu, int64_t
   SFT_CHECK(cu.scalar_type() == at::kInt && cu.is_cuda() && cu.dim() == 1 && cu.numel() >= 2, "cu_seqlens int32");
 }
 
+// Sliding window: query i sees keys (i - window, i]; 0 = no window. A window that covers the longest sequence is the
+// plain causal mask and runs the plain kernels (returns 0).
+static int attn_window(int64_t window, bool causal, int64_t max_seqlen) {
+  SFT_CHECK(window >= 0, "flash attention: window must be >= 0, got ", window);
+  SFT_CHECK(window == 0 || causal, "flash attention: a sliding window requires causal=True");
+  return window < max_seqlen ? (int)window : 0;
+}
+
 // The default backward stores the bf16 dS^T blocks of every (sequence, head) — nseq x nq x lp^2 x 2 bytes (134 MB for
 // 16 x 512 tokens, 16 heads); past SFTAMD_ATTN_DS_MB (default 2048, read per call so tests can switch paths
 // in-process) the dq3 kernel recomputes S / dP instead (long contexts).
@@ -901,8 +953,10 @@ static long attn_ds_budget() {
 
 // forward: fwd32 (4 waves = HW GQA heads x 4 / HW 32-query blocks sharing each K / V tile)
 std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Tensor& cu, int64_t max_seqlen,
-                                             int64_t nq, int64_t nkv, int64_t hd, double scale, bool causal) {
+                                             int64_t nq, int64_t nkv, int64_t hd, double scale, bool causal,
+                                             int64_t window) {
   check_attn_args(qkv, cu, nq, nkv, hd);
+  const int win = attn_window(window, causal, max_seqlen);
   const int total = qkv.size(0);
   const int nseq = cu.numel() - 1;
   auto out = at::empty({total, nq * hd}, qkv.options());
@@ -918,9 +972,18 @@ std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Te
   SFT_TRACE("attn.fwd32");
   const int rep = nq / nkv, hw = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1, span = 32 * (4 / hw);
   dim3 g(nq / hw, nseq, (max_seqlen + span - 1) / span);
-  if (hw == 4) attn::fwd32_kernel<4><<<g, 256, 0, cur_stream()>>>(q, o, lp, cp, nq, nkv, total, sl2, ca);
-  else if (hw == 2) attn::fwd32_kernel<2><<<g, 256, 0, cur_stream()>>>(q, o, lp, cp, nq, nkv, total, sl2, ca);
-  else attn::fwd32_kernel<1><<<g, 256, 0, cur_stream()>>>(q, o, lp, cp, nq, nkv, total, sl2, ca);
+#define SFT_FWD32(HW, WIN) \
+  attn::fwd32_kernel<HW, WIN><<<g, 256, 0, cur_stream()>>>(q, o, lp, cp, nq, nkv, total, sl2, WIN ? win : ca)
+  if (win > 0) {
+    if (hw == 4) SFT_FWD32(4, true);
+    else if (hw == 2) SFT_FWD32(2, true);
+    else SFT_FWD32(1, true);
+  } else {
+    if (hw == 4) SFT_FWD32(4, false);
+    else if (hw == 2) SFT_FWD32(2, false);
+    else SFT_FWD32(1, false);
+  }
+#undef SFT_FWD32
   SFT_LAUNCH_CHECK();
   return {out, lse};
 }
@@ -932,9 +995,11 @@ std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Te
 static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& out,
                                  const at::Tensor& lse, const at::Tensor& cu, int64_t max_seqlen, int64_t nq,
                                  int64_t nkv, int64_t hd, double scale, bool causal, const float* rcos,
-                                 const float* rsin, bool& rope_done, const c10::optional<at::Tensor>& delta_in) {
+                                 const float* rsin, bool& rope_done, const c10::optional<at::Tensor>& delta_in,
+                                 int64_t window) {
   rope_done = false;
   check_attn_args(qkv, cu, nq, nkv, hd);
+  const int win = attn_window(window, causal, max_seqlen);
   SFT_CHECK_CONTIG(dout);
   SFT_CHECK_CONTIG(out);
   SFT_CHECK(dout.sizes() == out.sizes() && out.size(1) == nq * hd, "dout/out shape");
@@ -971,7 +1036,7 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
     if (rope) SFT_TRACE("attn.bwd_rope_epi");
     attn::launch_dkdv(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(), cu_c.data_ptr<int>(),
                        (u16*)dqkv.data_ptr(), nq, nkv, total, nseq, max_seqlen, sl2, (float)scale, causal ? 1 : 0,
-                       (u16*)dst.data_ptr(), (int)lp, cur_stream(), rcos, rsin);
+                       (u16*)dst.data_ptr(), (int)lp, cur_stream(), win, rcos, rsin);
     SFT_LAUNCH_CHECK();
     {
       const int rep = nq / nkv, hw = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1, span = 32 * (4 / hw);
@@ -980,9 +1045,19 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
       u16* dx = (u16*)dqkv.data_ptr();
       const int* cp = cu_c.data_ptr<int>();
       const int ca = causal ? 1 : 0;
-      if (hw == 4) attn::bwd_dq32_kernel<4><<<g, 256, 0, cur_stream()>>>(q, ds, cp, dx, nq, nkv, (int)lp, (float)scale, ca, rcos, rsin);
-      else if (hw == 2) attn::bwd_dq32_kernel<2><<<g, 256, 0, cur_stream()>>>(q, ds, cp, dx, nq, nkv, (int)lp, (float)scale, ca, rcos, rsin);
-      else attn::bwd_dq32_kernel<1><<<g, 256, 0, cur_stream()>>>(q, ds, cp, dx, nq, nkv, (int)lp, (float)scale, ca, rcos, rsin);
+#define SFT_DQ32(HW, WIN)                                                                                        \
+  attn::bwd_dq32_kernel<HW, WIN><<<g, 256, 0, cur_stream()>>>(q, ds, cp, dx, nq, nkv, (int)lp, (float)scale,   \
+                                                              WIN ? win : ca, rcos, rsin)
+      if (win > 0) {
+        if (hw == 4) SFT_DQ32(4, true);
+        else if (hw == 2) SFT_DQ32(2, true);
+        else SFT_DQ32(1, true);
+      } else {
+        if (hw == 4) SFT_DQ32(4, false);
+        else if (hw == 2) SFT_DQ32(2, false);
+        else SFT_DQ32(1, false);
+      }
+#undef SFT_DQ32
     }
     SFT_LAUNCH_CHECK();
     rope_done = rope;
@@ -990,23 +1065,28 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
   }
   SFT_TRACE("attn.dq3");
   dim3 gq3(nq, nseq, (max_seqlen + 127) / 128);
-  attn::bwd_dq3_kernel<8><<<gq3, 512, 0, cur_stream()>>>(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(),
-                                                         cu_c.data_ptr<int>(), (u16*)dqkv.data_ptr(), nq, nkv, total,
-                                                         sl2, (float)scale, causal ? 1 : 0);
+  if (win > 0)
+    attn::bwd_dq3_kernel<8, true><<<gq3, 512, 0, cur_stream()>>>(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(),
+                                                                 cu_c.data_ptr<int>(), (u16*)dqkv.data_ptr(), nq, nkv,
+                                                                 total, sl2, (float)scale, win);
+  else
+    attn::bwd_dq3_kernel<8, false><<<gq3, 512, 0, cur_stream()>>>(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(),
+                                                                  cu_c.data_ptr<int>(), (u16*)dqkv.data_ptr(), nq, nkv,
+                                                                  total, sl2, (float)scale, causal ? 1 : 0);
   SFT_LAUNCH_CHECK();
   attn::launch_dkdv(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(), cu_c.data_ptr<int>(),
                      (u16*)dqkv.data_ptr(), nq, nkv, total, nseq, max_seqlen, sl2, (float)scale, causal ? 1 : 0,
-                     nullptr, 0, cur_stream());
+                     nullptr, 0, cur_stream(), win);
   SFT_LAUNCH_CHECK();
   return dqkv;
 }
 
 at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& lse,
                      const at::Tensor& cu, int64_t max_seqlen, int64_t nq, int64_t nkv, int64_t hd, double scale,
-                     bool causal, const c10::optional<at::Tensor>& delta) {
+                     bool causal, const c10::optional<at::Tensor>& delta, int64_t window) {
   bool rope_done;
   return flash_bwd_impl(dout, qkv, out, lse, cu, max_seqlen, nq, nkv, hd, scale, causal, nullptr, nullptr, rope_done,
-                        delta);
+                        delta, window);
 }
 
 // flash_bwd for a qkv whose q / k heads were rotated (RoPE) by the producing GEMM: returns the gradient w.r.t. the
@@ -1015,14 +1095,14 @@ at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Te
 at::Tensor flash_bwd_rope(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& lse,
                           const at::Tensor& cu, int64_t max_seqlen, int64_t nq, int64_t nkv, int64_t hd, double scale,
                           bool causal, const at::Tensor& cos, const at::Tensor& sin,
-                          const c10::optional<at::Tensor>& delta) {
+                          const c10::optional<at::Tensor>& delta, int64_t window) {
   SFT_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
                 sin.is_contiguous() && cos.is_cuda() && sin.is_cuda(),
             "flash_bwd_rope: contiguous fp32 cos / sin");
   SFT_CHECK(cos.numel() == qkv.size(0) * hd / 2 && sin.numel() == cos.numel(), "flash_bwd_rope: cos / sin [total, hd/2]");
   bool rope_done;
   auto dqkv = flash_bwd_impl(dout, qkv, out, lse, cu, max_seqlen, nq, nkv, hd, scale, causal, cos.data_ptr<float>(),
-                             sin.data_ptr<float>(), rope_done, delta);
+                             sin.data_ptr<float>(), rope_done, delta, window);
   if (!rope_done) rope_(dqkv, cos, sin, nq, nkv, hd, true);
   return dqkv;
 }

@@ -89,12 +89,12 @@ TORCH_LIBRARY(sftamd, m) {
   // loss
   // label_smoothing e in [0, 1) (HF LabelSmoother) or loss_mode 1 = dft (TRL dft_loss); stats row 0 is the objective
   m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0) -> Tensor");
-  // attention
-  m.def("flash_fwd(Tensor qkv, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal) -> (Tensor, Tensor)");
-  m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None) -> Tensor");
-  m.def("flash_bwd_rope(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor cos, Tensor sin, Tensor? delta=None) -> Tensor");
-  m.def("decode_attention(Tensor q, Tensor kcache, Tensor vcache, Tensor cache_len, int n_q, int n_kv, float scale) -> Tensor");
-  m.def("decode_attention_batched(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor lens, int n_q, int n_kv, float scale) -> Tensor");
+  // attention (window > 0: causal sliding window, query i sees keys (i - window, i]; 0: none)
+  m.def("flash_fwd(Tensor qkv, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, int window=0) -> (Tensor, Tensor)");
+  m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None, int window=0) -> Tensor");
+  m.def("flash_bwd_rope(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor cos, Tensor sin, Tensor? delta=None, int window=0) -> Tensor");
+  m.def("decode_attention(Tensor q, Tensor kcache, Tensor vcache, Tensor cache_len, int n_q, int n_kv, float scale, int window=0) -> Tensor");
+  m.def("decode_attention_batched(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor lens, int n_q, int n_kv, float scale, int window=0) -> Tensor");
   // fused decode sampler: penalty -> temperature -> top-k -> top-p -> draw, device-resident state
   m.def("sample_token(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");
   m.def("sample_tokens(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, Tensor(g!) done, int eos_token_id, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");

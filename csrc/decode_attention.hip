@@ -21,10 +21,12 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 // One (split, kv head) workgroup of one sequence; shared by the single-sequence and the batched kernel.
 // q: [nq*D] bf16; kc/vc: [S_max, nkv, D] bf16; po: [rep, D] f32; pml: [rep, 2] f32 (this block's partials)
+// window > 0 (sliding window): the live keys are [max(0, len - window), len); a chunk wholly below them is empty,
+// the chunk that straddles the edge masks its low keys.
 __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16* __restrict__ kc,
                                            const u16* __restrict__ vc, const int len, float* __restrict__ po,
                                            float* __restrict__ pml, const int split, const int kvh, int nq, int nkv,
-                                           float sl2) {
+                                           float sl2, int window) {
   __shared__ float qs[MAXREP][D];
   __shared__ float ps[MAXREP][CHUNK];
   __shared__ float red[MAXREP][8];
@@ -32,7 +34,8 @@ __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16*
   const int rep = nq / nkv;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int k0 = split * CHUNK;
-  if (k0 >= len) {  // empty chunk: neutral element for the combine
+  const int lo = window > 0 ? max(len - window, 0) : 0;  // first live key
+  if (k0 >= len || k0 + CHUNK <= lo) {  // empty chunk: neutral element for the combine
     if (tid < rep) {
       pml[tid * 2] = -INFINITY;
       pml[tid * 2 + 1] = 0.f;
@@ -45,7 +48,8 @@ __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16*
   float s[MAXREP];
 #pragma unroll
   for (int h = 0; h < MAXREP; ++h) s[h] = -INFINITY;
-  if (key < len) {
+  const bool live = key < len && key >= lo;
+  if (live) {
     const u16* kr = kc + ((long)key * nkv + kvh) * D;
 #pragma unroll
     for (int h = 0; h < MAXREP; ++h) s[h] = 0.f;
@@ -76,7 +80,7 @@ __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16*
   __syncthreads();
 #pragma unroll
   for (int h = 0; h < MAXREP; ++h) {
-    const float p = (h < rep && key < len) ? exp2f(s[h] - m[h]) : 0.f;
+    const float p = (h < rep && live) ? exp2f(s[h] - m[h]) : 0.f;
     if (h < rep) ps[h][tid] = p;
     const float v = wave_sum(p);
     if (lane == 0) red[h][4 + wave] = v;
@@ -90,7 +94,7 @@ __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16*
 #pragma unroll
   for (int h = 0; h < MAXREP; ++h) a[h] = 0.f;
   const int nk = min(CHUNK, len - k0);
-  for (int t = kh; t < nk; t += 2) {
+  for (int t = max(lo - k0, 0) + kh; t < nk; t += 2) {
     const float v = bf2f(vc[((long)(k0 + t) * nkv + kvh) * D + d]);
 #pragma unroll
     for (int h = 0; h < MAXREP; ++h)
@@ -113,11 +117,11 @@ __device__ __forceinline__ void split_body(const u16* __restrict__ q, const u16*
 __global__ __launch_bounds__(256) void split_kernel(const u16* __restrict__ q, const u16* __restrict__ kc,
                                                     const u16* __restrict__ vc, const int* __restrict__ len_p,
                                                     float* __restrict__ part_o, float* __restrict__ part_ml, int nq,
-                                                    int nkv, float sl2) {
+                                                    int nkv, float sl2, int window) {
   const int split = blockIdx.x, kvh = blockIdx.y, splits = gridDim.x;
   const int rep = nq / nkv;
   split_body(q, kc, vc, *len_p, part_o + ((long)(kvh * splits + split) * rep) * D,
-             part_ml + ((long)(kvh * splits + split) * rep) * 2, split, kvh, nq, nkv, sl2);
+             part_ml + ((long)(kvh * splits + split) * rep) * 2, split, kvh, nq, nkv, sl2, window);
 }
 
 // Merge of one query head's splits. EMPTY_OK: a sequence with no live key (every chunk empty) gives zeros, not 0/0.
@@ -175,14 +179,14 @@ __global__ __launch_bounds__(256) void append_kernel(const u16* __restrict__ qkv
 __global__ __launch_bounds__(256) void split_batched_kernel(const u16* __restrict__ qkv, const u16* __restrict__ kc,
                                                             const u16* __restrict__ vc, const int* __restrict__ lens,
                                                             float* __restrict__ part_o, float* __restrict__ part_ml,
-                                                            int nq, int nkv, int smax, float sl2) {
+                                                            int nq, int nkv, int smax, float sl2, int window) {
   const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z, splits = gridDim.x;
   const int rep = nq / nkv;
   const int len = min(lens[b], smax);  // never read past the slab; <= 0 leaves every chunk empty
   const long blk = ((long)b * nkv + kvh) * splits + split;
   const long slab = (long)b * smax * nkv * D;
   split_body(qkv + (long)b * (nq + 2 * nkv) * D, kc + slab, vc + slab, len, part_o + blk * rep * D,
-             part_ml + blk * rep * 2, split, kvh, nq, nkv, sl2);
+             part_ml + blk * rep * 2, split, kvh, nq, nkv, sl2, window);
 }
 
 // grid (nq, B)
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(128) void combine_batched_kernel(const float* __res
 }  // namespace decode
 
 at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                            const at::Tensor& cache_len, int64_t nq, int64_t nkv, double scale) {
+                            const at::Tensor& cache_len, int64_t nq, int64_t nkv, double scale, int64_t window) {
   SFT_CHECK_BF16(q);
   SFT_CHECK_BF16(kcache);
   SFT_CHECK(q.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous(), "contiguous");
@@ -205,7 +209,9 @@ at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const
   SFT_CHECK(q.numel() == nq * decode::D, "q must be [nq*128]");
   SFT_CHECK(nq % nkv == 0 && nq / nkv <= decode::MAXREP, "GQA ratio <= 8");
   SFT_CHECK(cache_len.scalar_type() == at::kInt && cache_len.is_cuda(), "cache_len int32 on device");
+  SFT_CHECK(window >= 0, "decode_attention: window must be >= 0");
   const int smax = kcache.size(0);
+  const int win = window < smax ? (int)window : 0;  // a window that covers the cache is no window
   const int splits = (smax + decode::CHUNK - 1) / decode::CHUNK;
   const int rep = nq / nkv;
   auto po = at::empty({nkv * splits * rep * decode::D}, q.options().dtype(at::kFloat));
@@ -213,7 +219,7 @@ at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const
   auto out = at::empty({nq * decode::D}, q.options());
   decode::split_kernel<<<dim3(splits, nkv), 256, 0, cur_stream()>>>(
       (const u16*)q.data_ptr(), (const u16*)kcache.data_ptr(), (const u16*)vcache.data_ptr(), cache_len.data_ptr<int>(),
-      po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, (float)scale * decode::LOG2E);
+      po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, (float)scale * decode::LOG2E, win);
   SFT_LAUNCH_CHECK();
   decode::combine_kernel<<<nq, 128, 0, cur_stream()>>>(po.data_ptr<float>(), pml.data_ptr<float>(),
                                                        (u16*)out.data_ptr(), nq, nkv, splits);
@@ -225,7 +231,7 @@ at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const
 // qkv [B, (nq + 2 nkv) * 128] (post-RoPE), kcache / vcache [B, S_max, nkv, 128], lens int32 [B] on the device
 // (live length INCLUDING the token being decoded). Static shapes, no host sync: lives inside a captured graph.
 at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at::Tensor vcache, const at::Tensor& lens,
-                                    int64_t nq, int64_t nkv, double scale) {
+                                    int64_t nq, int64_t nkv, double scale, int64_t window) {
   SFT_CHECK_CUDA(qkv);
   SFT_CHECK_BF16(qkv);
   SFT_CHECK_BF16(kcache);
@@ -244,6 +250,8 @@ at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at
                 (uintptr_t)vcache.data_ptr() % 16 == 0, "16-byte aligned");
   const int smax = kcache.size(1);
   SFT_CHECK(smax >= 1, "empty cache");
+  SFT_CHECK(window >= 0, "decode_attention_batched: window must be >= 0");
+  const int win = window < smax ? (int)window : 0;  // a window that covers the slab is no window
   const int splits = (smax + decode::CHUNK - 1) / decode::CHUNK;
   const int rep = nq / nkv;
   auto po = at::empty({B * nkv * splits * rep * decode::D}, qkv.options().dtype(at::kFloat));
@@ -254,7 +262,7 @@ at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at
   SFT_LAUNCH_CHECK();
   decode::split_batched_kernel<<<dim3(splits, nkv, B), 256, 0, cur_stream()>>>(
       (const u16*)qkv.data_ptr(), (const u16*)kcache.data_ptr(), (const u16*)vcache.data_ptr(), lens.data_ptr<int>(),
-      po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, smax, (float)scale * decode::LOG2E);
+      po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, smax, (float)scale * decode::LOG2E, win);
   SFT_LAUNCH_CHECK();
   decode::combine_batched_kernel<<<dim3(nq, B), 128, 0, cur_stream()>>>(po.data_ptr<float>(), pml.data_ptr<float>(),
                                                                         (u16*)out.data_ptr(), nq, nkv, splits);

@@ -45,6 +45,12 @@ def _heads(cfg):
     return cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
 
 
+def _windows(model) -> List[int]:
+    """Every layer's sliding window (0: none), as its Attention module holds it. The cache stays a full-length slab
+    either way: a window only narrows the rows a step attends over."""
+    return [layer.self_attn.window for layer in model.model.layers]
+
+
 def _kv_rows(cfg, qkv: torch.Tensor):
     """The k and v columns of the packed qkv [M, (nq + 2 nkv) D] as [M, nkv, D] views."""
     nq, nkv, D = _heads(cfg)
@@ -90,6 +96,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, prefill: bool) -> t
     """ids: [M] tokens appended at positions cache.len ... Returns last-token logits [V] (fp32)."""
     nq, nkv, D = _heads(model.config)
     M, s = ids.numel(), cache.len
+    W = _windows(model)
     cu = torch.tensor([0, M], dtype=torch.int32, device=ids.device) if prefill else None
 
     def store(li, qkv):
@@ -97,13 +104,14 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, prefill: bool) -> t
 
     def attend_prefill(li, qkv):
         store(li, qkv)
-        return ops.flash_attention(qkv.contiguous(), cu, M, nq, nkv, D)
+        return ops.flash_attention(qkv.contiguous(), cu, M, nq, nkv, D, window=W[li])
 
     def attend_decode(li, qkv):  # one row, eagerly in fp32 over the cache (the CPU path's decode step)
         store(li, qkv)
         q = qkv[:, :nq * D].view(nq, D).float()
-        K = cache.k[li, :s + 1].float()  # [S, nkv, D]
-        V = cache.v[li, :s + 1].float()
+        lo = max(0, s + 1 - W[li]) if W[li] else 0  # the layer's sliding window: the last W rows
+        K = cache.k[li, lo:s + 1].float()  # [S, nkv, D]
+        V = cache.v[li, lo:s + 1].float()
         att = torch.einsum("grd,sgd->grs", q.view(nkv, nq // nkv, D), K) / math.sqrt(D)
         return torch.einsum("grs,sgd->grd", att.softmax(-1), V).reshape(1, nq * D).to(qkv.dtype)
 
@@ -211,6 +219,7 @@ class GraphDecoder:
         self.len = torch.ones(1, dtype=torch.int32, device=dev)
         self.graph = None
         self.logits = None
+        self.windows = _windows(model)  # launch constants of the decode op: the captured graph stays shape-static
 
     def _attend(self, li: int, qkv: torch.Tensor) -> torch.Tensor:
         nq, nkv, D = _heads(self.model.config)
@@ -218,7 +227,7 @@ class GraphDecoder:
         self.cache.k[li].index_copy_(0, self.pos, k)
         self.cache.v[li].index_copy_(0, self.pos, v)
         return ops.decode_attention(qkv[0, :nq * D].contiguous(), self.cache.k[li], self.cache.v[li], self.len,
-                                    nq, nkv).view(1, nq * D)
+                                    nq, nkv, window=self.windows[li]).view(1, nq * D)
 
     def _step(self) -> torch.Tensor:
         x, residual = _run_layers(self.model, self.tok, self.pos, self._attend)
@@ -334,6 +343,7 @@ def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch
     uses; K/V are scattered into each sequence's slab. Returns the last-token logits [B, V] (fp32)."""
     dev = model.model.embed_tokens.device
     nq, nkv, D = _heads(model.config)
+    W = _windows(model)
     n = [len(p) for p in prompts]
     assert len(n) == len(cache.lens) and min(n) > 0 and max(n) <= cache.k.shape[2], "prompts do not fit the cache"
     ids = torch.tensor([t for p in prompts for t in p], device=dev)
@@ -346,7 +356,7 @@ def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch
 
     def attend(li, qkv):
         cache.k[li][seq, pos], cache.v[li][seq, pos] = _kv_rows(model.config, qkv)
-        return ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D)
+        return ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D, window=W[li])
 
     x, residual = _run_layers(model, ids, pos, attend)
     cache.lens = list(n)
@@ -391,10 +401,12 @@ class BatchGraphDecoder:
         self.graph = None          # model step only (step())
         self.sampled_graph = None  # model step + sampler (run_sampled())
         self.logits = None
+        self.windows = _windows(model)  # launch constants, as in GraphDecoder
 
     def _attend(self, li: int, qkv: torch.Tensor) -> torch.Tensor:  # the op appends each row's K/V itself
         nq, nkv, _ = _heads(self.model.config)
-        return ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv)
+        return ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv,
+                                            window=self.windows[li])
 
     def _step(self) -> torch.Tensor:
         return _logits(self.model, *_run_layers(self.model, self.tok, self.pos, self._attend))

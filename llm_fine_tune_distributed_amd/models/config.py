@@ -45,6 +45,10 @@ class ModelConfig:
     # Learned bias on the q, k and v projections (not on o_proj), added before RoPE (Qwen2 / Qwen2.5:
     # self_attn.{q,k,v}_proj.bias). None: decided by the model type.
     qkv_bias: Optional[bool] = None
+    # Sliding-window attention (Mistral): the query at position i sees the keys j with i - W < j <= i, W keys with
+    # itself (transformers' sliding_window_overlay). None: full causal attention. Every layer has the same window;
+    # each Attention module reads its own (Attention.window), so a per-layer list would only change that one read.
+    sliding_window: Optional[int] = None
     extra: Dict[str, Any] = field(default_factory=dict)
 
     def __post_init__(self):
@@ -63,6 +67,10 @@ class ModelConfig:
             else:
                 self.no_rope_layers = [1] * self.num_hidden_layers
         assert len(self.no_rope_layers) >= self.num_hidden_layers
+        if self.sliding_window is not None:
+            self.sliding_window = int(self.sliding_window)
+            if self.sliding_window <= 0:
+                raise ValueError(f"sliding_window must be a positive number of keys or None, got {self.sliding_window}")
         assert self.num_attention_heads % self.num_key_value_heads == 0
 
     # ------------------------------------------------------------------ helpers
@@ -93,13 +101,19 @@ class ModelConfig:
         return self.num_hidden_layers * per_layer + emb + head + h
 
     def flops_per_token(self, seq_len: int, training: bool = True, recompute: bool = False) -> float:
-        """Analytic matmul FLOPs per token. Attention counted causal."""
+        """Analytic matmul FLOPs per token. Attention counted causal, and within the sliding window
+        where the model has one."""
         h = self.hidden_size
         dense = self.num_hidden_layers * (h * self.qkv_size + self.q_size * h + 3 * h * self.intermediate_size)
         dense += self.vocab_size * h
         fwd = 2.0 * dense
-        # causal attention: QK^T and PV, each 2*T*d per head per token, halved by the mask
-        fwd += self.num_hidden_layers * 2.0 * 2.0 * self.num_attention_heads * self.head_dim * seq_len / 2.0
+        # causal attention: QK^T and PV, each 2*T*d per head per token, halved by the mask (T^2 / 2 pairs). With a
+        # window W < T row i sees min(i + 1, W) keys instead of i + 1: exactly (T - W) (T - W + 1) / 2 pairs fewer.
+        keys = seq_len / 2.0
+        W = self.sliding_window
+        if W is not None and W < seq_len:
+            keys -= (seq_len - W) * (seq_len - W + 1) / 2.0 / seq_len
+        fwd += self.num_hidden_layers * 2.0 * 2.0 * self.num_attention_heads * self.head_dim * keys
         if not training:
             return fwd
         mult = 4.0 if recompute else 3.0
@@ -109,9 +123,13 @@ class ModelConfig:
     def to_hf_dict(self) -> Dict[str, Any]:
         arch = {"smollm3": "SmolLM3ForCausalLM", "llama": "LlamaForCausalLM",
                 "qwen3": "Qwen3ForCausalLM", "qwen2": "Qwen2ForCausalLM"}.get(self.model_type, "LlamaForCausalLM")
+        mtype = self.model_type
+        if mtype == "llama" and self.sliding_window is not None:
+            # Llama plus a window is Mistral (same weight names): transformers loads it with the same mask
+            arch, mtype = "MistralForCausalLM", "mistral"
         d = {
             "architectures": [arch],
-            "model_type": self.model_type,
+            "model_type": mtype,
             "vocab_size": self.vocab_size,
             "hidden_size": self.hidden_size,
             "intermediate_size": self.intermediate_size,
@@ -136,6 +154,9 @@ class ModelConfig:
         if self.model_type == "smollm3":
             d["no_rope_layers"] = list(self.no_rope_layers[: self.num_hidden_layers])
             d["no_rope_layer_interval"] = self.no_rope_layer_interval
+        if mtype == "mistral":
+            del d["mlp_bias"], d["attention_bias"]  # not MistralConfig keys
+            d["sliding_window"] = self.sliding_window
         if self.model_type == "qwen3":
             del d["mlp_bias"]  # not a Qwen3Config key
             d["use_sliding_window"] = False
@@ -160,8 +181,17 @@ class ModelConfig:
             kw["eos_token_id"] = kw["eos_token_id"][0]
         kw.setdefault("model_type", d.get("model_type", "llama"))
         if kw["model_type"] not in ("smollm3", "llama", "qwen3", "qwen2"):
-            kw["model_type"] = "llama"
+            kw["model_type"] = "llama"  # (mistral among them: Llama's weights plus sliding_window, read below)
         mt = kw["model_type"]
+        kw.pop("sliding_window", None)
+        if mt == "llama":
+            # Mistral: sliding_window (missing or null: full attention). One window for every layer: a layer_types
+            # list may only repeat one type.
+            if len(set(d.get("layer_types") or [])) > 1:
+                raise NotImplementedError(f"layer_types {sorted(set(d['layer_types']))}: mixed layer types are not "
+                                          "supported (one attention type for every layer)")
+            if d.get("sliding_window") is not None and set(d.get("layer_types") or []) != {"full_attention"}:
+                kw["sliding_window"] = int(d["sliding_window"])
         if mt in ("qwen3", "qwen2"):
             # what a Qwen config may ask for and this model does not implement: fail here, not in the weights loader
             if mt == "qwen3" and d.get("attention_bias"):
@@ -252,6 +282,19 @@ def qwen2_5_7b() -> ModelConfig:
                     num_key_value_heads=4, vocab_size=152064, tie_word_embeddings=False)
 
 
+# Written from memory of the published config.json, like the Qwen shapes above (no copy of it was at hand): a real
+# checkpoint directory's own config.json always wins (get_config on the directory).
+def mistral_7b() -> ModelConfig:
+    """mistralai/Mistral-7B-v0.1 shape: Llama's architecture (model_type "llama" here) plus a 4096-key sliding
+    window; saved as MistralForCausalLM."""
+    return ModelConfig(
+        model_type="llama", vocab_size=32000, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
+        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rope_theta=10000.0, rms_norm_eps=1e-5,
+        max_position_embeddings=32768, tie_word_embeddings=False, bos_token_id=1, eos_token_id=2, pad_token_id=None,
+        sliding_window=4096,
+    )
+
+
 def tiny(model_type: str = "smollm3", **kw) -> ModelConfig:
     """Small config with the same structure (GQA, NoPE interval, tied head) for tests."""
     base = dict(
@@ -290,6 +333,13 @@ PRESETS = {
     "tiny-qwen2": lambda: tiny("qwen2"),
     "tiny-gpu-qwen2": lambda: tiny("qwen2", hidden_size=256, num_attention_heads=2, num_key_value_heads=1,
                                    head_dim=128, intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
+    "mistral-7b": mistral_7b,
+    "mistralai/Mistral-7B-v0.1": mistral_7b,
+    "tiny-mistral": lambda: tiny("llama", sliding_window=8),
+    # head_dim 128, GQA 4 (the forward's four waves share their positions), a window below one 64-key tile
+    "tiny-gpu-mistral": lambda: tiny("llama", hidden_size=256, num_attention_heads=4, num_key_value_heads=1,
+                                     head_dim=128, intermediate_size=512, vocab_size=1024, num_hidden_layers=2,
+                                     sliding_window=40),
 }
 
 

@@ -61,6 +61,9 @@ class Attention(nn.Module):
         assert not (self.qk_norm and self.has_qkv_bias), "qk_norm and qkv_bias are not implemented together"
         if self.has_qkv_bias:  # Qwen2: q_proj / k_proj / v_proj biases as one vector in the fused weight's row order
             self.qkv_bias = nn.Parameter(torch.zeros(cfg.qkv_size))
+        # sliding window of THIS layer (0: full causal attention), read per module: a per-layer schedule
+        # (Qwen's max_window_layers) would only change this line
+        self.window = int(cfg.sliding_window or 0)
         self.lora = None  # set by apply_lora
         self.cp_group = None  # context-parallel process group (CausalLM.enable_context_parallel)
         self.cp_layout = "zigzag"
@@ -87,6 +90,7 @@ class Attention(nn.Module):
         c = self.cfg
         nq, nkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         mid = self.qk_norm or self.has_qkv_bias  # a node between the projection and the rotation
+        win = {"window": self.window} if self.window else {}  # (a layer without a window makes the calls it made)
         assert self.use_rope or not mid, "qk-norm and qkv-bias layers rotate on every layer"
         if self.use_rope and not mid and self.cp_group is None:
             if self.lora is None:
@@ -95,12 +99,12 @@ class Attention(nn.Module):
                 # the o_proj backward computes the attention backward's delta in its dgrad epilogue (link: the hand-off)
                 link = ops.AttnLink()
                 a = ops.qkv_rope_attention(h, self.qkv_proj, rope_cs[0], rope_cs[1], cu_seqlens, max_seqlen, nq, nkv, D,
-                                           link=link)
+                                           link=link, **win)
                 return ops.attn_out_linear(a, self.o_proj, link)
             # the LoRA-widened qkv GEMM with the RoPE epilogue + attention as one node (inverse RoPE in the backward's
             # dq / dK epilogues), the plain composition where the HIP path does not apply
             a = ops.lora_qkv_rope_attention(h, self.qkv_proj, self.lora["qkv"], rope_cs[0], rope_cs[1], cu_seqlens,
-                                            max_seqlen, nq, nkv, D)
+                                            max_seqlen, nq, nkv, D, **win)
             return ops.lora_linear(a, self.o_proj, self.lora["o"])
         # The unfused composition: a NoPE layer, a layer with a mid node (the fused qkv + RoPE epilogue does not
         # apply), a context-parallel layer. With a link (no LoRA, no context-parallel group) the qkv node also issues
@@ -117,9 +121,10 @@ class Attention(nn.Module):
             qkv = self.rotate_qk_(qkv, rope_cs[0], rope_cs[1])
         if self.cp_group is not None:
             from ..parallel.context_parallel import ring_attention
+            assert self.window == 0, "ring attention has no sliding window (CausalLM.enable_context_parallel)"
             a = ring_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, self.cp_group, layout=self.cp_layout)
         else:
-            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, link=link)
+            a = ops.flash_attention(qkv, cu_seqlens, max_seqlen, nq, nkv, D, link=link, **win)
         if link is not None:
             return ops.attn_out_linear(a, self.o_proj, link)
         return ops.linear(a, self.o_proj) if self.lora is None else ops.lora_linear(a, self.o_proj, self.lora["o"])
@@ -226,7 +231,12 @@ class CausalLM(nn.Module):
     def enable_context_parallel(self, group, layout: str = "zigzag") -> None:
         """Attention over sequence chunks spread across ``group`` (ring attention, parallel/context_parallel.py).
         Inputs must then be this rank's chunk with explicit global ``position_ids`` and pre-shifted labels
-        (``context_parallel.shard_batch`` with the same ``layout``)."""
+        (``context_parallel.shard_batch`` with the same ``layout``). Ring attention has no sliding window: a
+        windowed model is rejected here."""
+        if self.config.sliding_window:
+            raise NotImplementedError(
+                f"sliding_window={self.config.sliding_window} with context parallelism is not supported: ring "
+                "attention implements full causal attention only (use context_parallel_size=1)")
         for layer in self.model.layers:
             layer.self_attn.cp_group = group
             layer.self_attn.cp_layout = layout

@@ -1222,44 +1222,54 @@ def qkv_bias_rope_(qkv, bias, cos, sin, n_q, n_kv, head_dim):
 # ----------------------------------------------------------------------------- attention
 class FlashAttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None):
-        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal)
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None, window=0):
+        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
         ctx.link = link
         if _ext.use_hip(qkv):
-            out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
+            out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
             ctx.save_for_backward(qkv, cu_seqlens, out, lse)
             ctx.hip = True
             if link is not None and head_dim == 128:
                 link.delta_ok = True
         else:
-            out = ref.attention(qkv, n_q, n_kv, head_dim, cu_seqlens, scale, causal)
+            out = ref.attention(qkv, n_q, n_kv, head_dim, cu_seqlens, scale, causal, window)
             ctx.save_for_backward(qkv, cu_seqlens)
             ctx.hip = False
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        max_seqlen, n_q, n_kv, hd, scale, causal = ctx.dims
+        max_seqlen, n_q, n_kv, hd, scale, causal, window = ctx.dims
         if ctx.hip:
             qkv, cu, out, lse = ctx.saved_tensors
             dqkv = _ext.ops().flash_bwd(dout.contiguous(), qkv, out, lse, cu, max_seqlen, n_q, n_kv, hd, scale, causal,
-                                        _take_delta(ctx.link, dout, n_q))
+                                        _take_delta(ctx.link, dout, n_q), window)
         else:
             qkv, cu = ctx.saved_tensors
             with torch.enable_grad():
                 q = qkv.detach().float().requires_grad_(True)
-                o = ref.attention(q, n_q, n_kv, hd, cu, scale, causal)
+                o = ref.attention(q, n_q, n_kv, hd, cu, scale, causal, window)
                 (dq,) = torch.autograd.grad(o, q, dout.float())
             dqkv = dq.to(qkv.dtype)
-        return dqkv, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
-def flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True, link=None):
+def _window(window, causal) -> int:
+    """The sliding window as the ops take it: 0 (or None) is no window, W > 0 needs the causal mask."""
+    window = int(window or 0)
+    if window < 0 or (window > 0 and not causal):
+        raise ValueError(f"attention: window={window} needs window >= 0 and causal=True")
+    return window
+
+
+def flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True, link=None, window=0):
     """link: a fresh AttnLink shared with attn_out_linear (the o_proj on this output): the o_proj backward computes
-    the attention backward's delta in its dgrad epilogue."""
+    the attention backward's delta in its dgrad epilogue. window: W > 0 is a sliding window, the query at position
+    i of its sequence sees the keys j with i - W < j <= i; 0 is no window."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    window = _window(window, causal)
     return FlashAttnFn.apply(qkv, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim, float(scale), bool(causal),
-                             link)
+                             link, *((window,) if window else ()))
 
 
 class QKVRopeAttnFn(Function):
@@ -1270,7 +1280,7 @@ class QKVRopeAttnFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None,
-                carry=None):
+                carry=None, window=0):
         ctx.link = link
         ctx.carry = carry
         if link is not None:
@@ -1279,40 +1289,42 @@ class QKVRopeAttnFn(Function):
                 link.qkv_takes_o_wgrad = True
         x2d = x.reshape(-1, x.shape[-1])
         qkv = _ext.ops().gemm_tn_rope(x2d, weight, cos, sin, (n_q + n_kv) * head_dim)
-        out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
+        out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
         ctx.save_for_backward(x2d, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.weight = weight
-        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal)
+        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
         ctx.x_shape = x.shape
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x2d, qkv, cu, out, lse, cos, sin = ctx.saved_tensors
-        max_seqlen, n_q, n_kv, hd, scale, causal = ctx.dims
+        max_seqlen, n_q, n_kv, hd, scale, causal, window = ctx.dims
         dqkv = _ext.ops().flash_bwd_rope(dout.contiguous(), qkv, out, lse, cu, max_seqlen, n_q, n_kv, hd, scale, causal,
-                                         cos, sin, _take_delta(ctx.link, dout, n_q))
+                                         cos, sin, _take_delta(ctx.link, dout, n_q), window)
         del qkv, out, lse
         dx, dw = _proj_backward(ctx.needs_input_grad, ctx.weight, dqkv, x2d, ctx.x_shape,
                                 pending=_take(ctx.link, "o_job"), sink=lambda jobs: _carry_or_launch(ctx.carry, jobs))
-        return dx, dw, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 _ROPE_ATTN_FUSED = True  # (a test seam: tests/test_model_gpu.py compares against the two separate nodes)
 
 
 def qkv_rope_attention(x, weight, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True,
-                       link=None):
+                       link=None, window=0):
     """flash_attention(linear_rope(x, W_qkv, cos, sin)) — one fused autograd node when the HIP paths apply
-    (the two separate nodes otherwise). link: see flash_attention."""
+    (the two separate nodes otherwise). link, window: see flash_attention."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    window = _window(window, causal)
     x2d = x.reshape(-1, x.shape[-1])
     if (_ROPE_ATTN_FUSED and _TN_MODE in ("1", "rope") and _tn_ok(x2d, weight)
             and _rope_epilogue_ok(x2d, weight, cos, sin, head_dim)):
         return QKVRopeAttnFn.apply(x, weight, cos, sin, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim,
-                                   float(scale), bool(causal), link, _carry_take() if link is not None else None)
+                                   float(scale), bool(causal), link, _carry_take() if link is not None else None,
+                                   *((window,) if window else ()))
     qkv = linear_rope(x, weight, cos, sin, n_q, n_kv, head_dim)
-    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link)
+    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link, window)
 
 
 # ----------------------------------------------------------------------------- LM head + CE
@@ -1853,44 +1865,45 @@ class LoRAQKVRopeAttnFn(Function):
     backward (base dgrad, adapter dx, dA / dB straight into main_grad) — no separate RoPE pass either way."""
 
     @staticmethod
-    def forward(ctx, x, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, wide, K, scaling, p,
-                seed, meta, *ab):
+    def forward(ctx, x, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, window, wide, K,
+                scaling, p, seed, meta, *ab):
         X, acat, state = _lora_wide_prep(x, wide, K, scaling, p, seed, meta, ab)
         qkv = _ext.ops().gemm_tn_rope(X, wide, cos, sin, (n_q + n_kv) * head_dim)
-        out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
+        out, lse = _ext.ops().flash_fwd(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
         ctx.save_for_backward(X, acat, qkv, cu_seqlens, out, lse, cos, sin)
         ctx.wide, ctx.adapters, ctx.meta = wide, ab, state
-        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal)
+        ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal, window)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         X, acat, qkv, cu, out, lse, cos, sin = ctx.saved_tensors
-        max_seqlen, n_q, n_kv, hd, scale, causal = ctx.dims
+        max_seqlen, n_q, n_kv, hd, scale, causal, window = ctx.dims
         dqkv = _ext.ops().flash_bwd_rope(dout.contiguous(), qkv, out, lse, cu, max_seqlen, n_q, n_kv, hd, scale, causal,
-                                         cos, sin)
+                                         cos, sin, None, window)
         del qkv, out, lse
         dx, dAs, dBs = _lora_wide_bwd(X, acat, ctx.wide, ctx.adapters, ctx.meta, dqkv, ctx.needs_input_grad[0])
         if dx is not None:
             dx = dx.view(ctx.meta[-1])
-        return (dx, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None,
+        return (dx, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None,
                 *dAs, *dBs)
 
 
 def lora_qkv_rope_attention(x, weight, lora, cos, sin, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None,
-                            causal=True):
+                            causal=True, window=0):
     """flash_attention(rope_(lora_linear(x, W_qkv, lora))) — one fused autograd node on the HIP wide path
-    (LoRAQKVRopeAttnFn), the composition of the three otherwise."""
+    (LoRAQKVRopeAttnFn), the composition of the three otherwise. window: see flash_attention."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    window = _window(window, causal)
     args = _lora_wide_args(lora, weight)
     x2d = x.reshape(-1, x.shape[-1])
     if (args is not None and _ROPE_ATTN_FUSED and args[0][0].shape[1] % 128 == 0
             and _rope_epilogue_ok(x2d, args[0][0], cos, sin, head_dim)):
         a, As, Bs = args
         return LoRAQKVRopeAttnFn.apply(x, cos, sin, cu_seqlens, int(max_seqlen), n_q, n_kv, head_dim, float(scale),
-                                       bool(causal), *a, *As, *Bs)
+                                       bool(causal), window, *a, *As, *Bs)
     qkv = rope_(lora_linear(x, weight, lora), cos, sin, n_q, n_kv, head_dim)
-    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal)
+    return flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, window=window)
 
 
 def lora_linear(x, weight, lora) -> torch.Tensor:
@@ -1903,29 +1916,34 @@ def lora_linear(x, weight, lora) -> torch.Tensor:
     return LoRALinearFn.apply(x, weight, float(lora.scaling), float(p), tuple(lora.out_splits), *lora.A, *lora.B)
 
 
-def decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, scale=None):
-    """Single-token GQA attention over cache[:cache_len] (cache_len: int32 device tensor)."""
+def decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, scale=None, window=0):
+    """Single-token GQA attention over cache[:cache_len] (cache_len: int32 device tensor); with a sliding window
+    W > 0 over its last W rows, cache[max(0, cache_len - W):cache_len]."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.numel() // n_q)
+    window = _window(window, True)
     if _ext.use_hip(q):
-        return _ext.ops().decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, float(scale))
+        return _ext.ops().decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, float(scale), window)
     L = int(cache_len.item())
+    lo = max(0, L - window) if window else 0
     D = q.numel() // n_q
     qg = q.float().view(n_kv, n_q // n_kv, D)
-    att = torch.einsum("grd,sgd->grs", qg, kcache[:L].float()) * scale
-    return torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[:L].float()).reshape(-1).to(q.dtype)
+    att = torch.einsum("grd,sgd->grs", qg, kcache[lo:L].float()) * scale
+    return torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[lo:L].float()).reshape(-1).to(q.dtype)
 
 
-def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None):
+def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None, window=0):
     """One decode step of B sequences. ``qkv`` [B, (n_q + 2 n_kv) * D] is the step's post-RoPE projection,
     ``kcache`` / ``vcache`` [B, S_max, n_kv, D] one slab per sequence, ``lens`` [B] int32 the live length of each
     sequence INCLUDING the token being decoded. Row b's K/V are appended at ``cache[b, lens[b] - 1]`` (a length
-    outside (0, S_max] skips the row), then row b attends over ``cache[b, :lens[b]]``. Returns [B, n_q * D].
+    outside (0, S_max] skips the row), then row b attends over ``cache[b, :lens[b]]`` (with a sliding ``window``
+    W > 0 over its last W rows, ``cache[b, max(0, lens[b] - W):lens[b]]``). Returns [B, n_q * D].
     The HIP kernel is built for head_dim 128; other head dims decode in torch, as they do in forward_cached."""
     B = qkv.shape[0]
     D = qkv.shape[1] // (n_q + 2 * n_kv)
+    window = _window(window, True)
     if _ext.use_hip(qkv) and D == 128:
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
-        return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale))
+        return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale), window)
     out = torch.zeros(B, n_q * D, dtype=qkv.dtype, device=qkv.device)
     smax = kcache.shape[1]
     for b, L in enumerate(lens.tolist()):
@@ -1934,7 +1952,8 @@ def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None):
         kcache[b, L - 1] = qkv[b, n_q * D:(n_q + n_kv) * D].view(n_kv, D)
         vcache[b, L - 1] = qkv[b, (n_q + n_kv) * D:].view(n_kv, D)
         qg = qkv[b, :n_q * D].float().view(n_kv, n_q // n_kv, D)
-        att = torch.einsum("grd,sgd->grs", qg, kcache[b, :L].float())
+        lo = max(0, L - window) if window else 0
+        att = torch.einsum("grd,sgd->grs", qg, kcache[b, lo:L].float())
         att = att / math.sqrt(D) if scale is None else att * scale  # the default divides, as forward_cached does
-        out[b] = torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[b, :L].float()).reshape(-1).to(qkv.dtype)
+        out[b] = torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[b, lo:L].float()).reshape(-1).to(qkv.dtype)
     return out

@@ -117,9 +117,14 @@ def qkv_bias_rope(qkv: torch.Tensor, bias: torch.Tensor, cos: torch.Tensor, sin:
 
 
 def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens: torch.Tensor,
-              scale: Optional[float] = None, causal: bool = True) -> torch.Tensor:
+              scale: Optional[float] = None, causal: bool = True, window: int = 0) -> torch.Tensor:
     """Varlen causal GQA attention on the packed qkv layout [M, (n_q+2n_kv)*D] -> [M, n_q*D]. Math in fp32 (fp64 for
-    fp64 inputs: the tests' reference), one rounding to the input dtype."""
+    fp64 inputs: the tests' reference), one rounding to the input dtype. ``window`` W > 0 is a sliding window: the
+    query at position i of its sequence sees the keys j with i - W < j <= i (W keys, itself included; transformers'
+    ``sliding_window_overlay``); 0 is no window. A window requires ``causal``."""
+    window = int(window or 0)
+    if window < 0 or (window > 0 and not causal):
+        raise ValueError(f"attention: window={window} needs window >= 0 and causal=True")
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
     M = qkv.shape[0]
@@ -140,6 +145,8 @@ def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens:
         if causal:
             T = e - s
             mask = torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril()
+            if window > 0:
+                mask &= ~torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril(-window)
             att = att.masked_fill(~mask, float("-inf"))
         p = att.softmax(-1)
         out[s:e] = (p @ vi).transpose(0, 1).to(qkv.dtype)
