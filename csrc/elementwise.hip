@@ -311,6 +311,7 @@ at::Tensor embedding_noise_fwd(const at::Tensor& ids, const at::Tensor& w, const
   sizes.push_back(H);
   auto out = at::empty(sizes, w.options());
   if (M == 0) return out;
+  SFT_TRACE("ew.embedding_noise.fwd");
   embedding_noise_fwd_kernel<<<ew_grid(M * H / 8), 256, 0, cur_stream()>>>(
       idc.data_ptr<int64_t>(), (const u16*)w.data_ptr(), mag.data_ptr<float>(), (u16*)out.data_ptr(), M, H, w.size(0),
       (unsigned)seed);
@@ -406,6 +407,7 @@ at::Tensor dropout_add(const c10::optional<at::Tensor>& a, const at::Tensor& b, 
   float scale;
   const unsigned thresh = drop_thresh16(p, &scale);
   dim3 grid((K / 8 + 255) / 256, (unsigned)std::min<long>(T, 65535));
+  SFT_TRACE("ew.dropout_add");
   dropout_add_kernel<<<grid, 256, 0, cur_stream()>>>(ap, lda, (const u16*)b.data_ptr(), b.stride(0), (u16*)out.data_ptr(),
                                                      K, T, K, thresh, scale, (unsigned)seed);
   SFT_LAUNCH_CHECK();

@@ -507,6 +507,7 @@ static void launch_fwd(const u16* x, long ldx, int copy, const at::Tensor& A, u1
   const unsigned thresh = thresh_of(p, &dscale);
   const int grid = (int)((T + 15) / 16);
   const u16* Ap = (const u16*)A.data_ptr();
+  SFT_TRACE(p > 0 ? "lora.fwd.dropout" : "lora.fwd");
 #define LORA_FWD(RF)                                                                                              \
   if (!swiglu && K == 2048)                                                                                       \
     fwd_kernel<RF, false, 4><<<grid, 512, 0, cur_stream()>>>(x, Ap, X, xdp, T, K, ldX, (float)s, thresh, dscale,  \
@@ -1051,6 +1052,7 @@ void copy2d_batch(const at::Tensor& desc, int64_t max_elems) {
   SFT_CHECK(n <= 65535, "copy2d_batch: at most 65535 copies per launch");
   if (n == 0 || max_elems <= 0) return;
   dim3 grid((unsigned)std::min(64L, (long)((max_elems + 255) / 256)), (unsigned)n);
+  SFT_TRACE("lora.copy2d_batch");
   lora::copy2d_batch_kernel<<<grid, 256, 0, cur_stream()>>>((const long long*)desc.data_ptr());
   SFT_LAUNCH_CHECK();
 }

@@ -298,6 +298,8 @@ void adamw_flat(at::Tensor param, const at::Tensor& grad, const c10::optional<at
     if (bf16m) go(ms, sr, std::true_type());
     else go(ms, sr, std::false_type());
   };
+  SFT_TRACE(std::string(has_master ? "optim.adamw.master" : sr_seed != 0 ? "optim.adamw.sr" : "optim.adamw.rn") +
+            (bf16m ? ".bf16m" : ".fp32m"));
   if (has_master) go2(std::true_type(), std::false_type());
   else if (sr_seed != 0) go2(std::false_type(), std::true_type());
   else go2(std::false_type(), std::false_type());

@@ -221,14 +221,28 @@ def rotate_checkpoints(output_dir: str, limit: Optional[int], best: Optional[str
             shutil.rmtree(p, ignore_errors=True)
 
 
-def load_checkpoint(path: str, model, optimizer, scheduler, rank: int):
-    from ..train.callbacks import TrainerState
+def load_weights(path: str, model, optimizer=None):
+    """The weights of the checkpoint (or HF directory) ``path`` into a live model, in the model's own dtype: the base
+    from ``model.safetensors``, the LoRA adapters from ``adapter_model.safetensors`` when both sides have them.
+    ``optimizer``: the one that updates this model. An overlapped update (or ZeRO-1 gather) still running on its side
+    stream is ordered before the writes, and its fp32 master copy, if it keeps one, restarts from the loaded
+    parameters; moments and step count stay (a weight restore: ``load_best_model_at_end``). ``load_checkpoint``
+    loads the saved optimizer state over that afterwards."""
+    if optimizer is not None:
+        optimizer.synchronize()
     sd = load_state_dict(path, device="cpu")
     with torch.no_grad():
         model.load_hf_state_dict({k: v.to(model.model.embed_tokens.dtype) for k, v in sd.items()}, strict=False)
         ad = os.path.join(path, "adapter_model.safetensors")
         if os.path.exists(ad):
             _load_lora(model, ad)
+    if optimizer is not None:
+        optimizer.refresh_master()
+
+
+def load_checkpoint(path: str, model, optimizer, scheduler, rank: int):
+    from ..train.callbacks import TrainerState
+    load_weights(path, model, optimizer)
     osd = torch.load(os.path.join(path, "optimizer.pt"), map_location="cpu", weights_only=True)
     optimizer.load_state_dict(osd)
     ssd = torch.load(os.path.join(path, "scheduler.pt"), weights_only=True)

@@ -247,8 +247,20 @@ class FlatAdamW:
                 "state_dtype": str(self.state_dtype).replace("torch.", ""), "lr": self.lr, "betas": self.betas,
                 "eps": self.eps, "weight_decay": self.weight_decay, "saved_world_size": e.world_size}
 
+    @torch.no_grad()
+    def refresh_master(self):
+        """Restart the fp32 master copy from the parameters as they are now: after weights were written into the model
+        from outside the optimizer (a checkpoint's), the next update must start from those, not from the master of the
+        last step. The ranges this rank holds state for (all of them, or the ZeRO-1 slices)."""
+        if self.master is None:
+            return
+        self.synchronize()
+        for s, t, lo in self._state_ranges():
+            self.master[lo:lo + t - s].copy_(self.engine.param_flat[s:t].float())
+
     def load_state_dict(self, sd: Dict):
         e = self.engine
+        self.synchronize()  # an overlapped update still writes the moments this fills
         self.step_count = int(sd["step"])
         ranges = self._state_ranges()
         dsts = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "master": self.master}

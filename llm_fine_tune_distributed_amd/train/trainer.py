@@ -650,9 +650,9 @@ class SFTTrainer:
                    if self.dist.device.type == "cuda" else 0.0}
         if a.load_best_model_at_end and self.state.best_model_checkpoint:
             self.heartbeat.pause()  # host-side load: nothing beats
-            sd = ckpt.load_state_dict(self.state.best_model_checkpoint, device="cpu")
-            with torch.no_grad():
-                self.model.load_hf_state_dict({k: v.to(torch.bfloat16) for k, v in sd.items()}, strict=False)
+            # a weight restore, not a resume: base and adapters in the model's dtype, the master copy re-seeded from
+            # them, moments / step count / scheduler as the last step left them
+            ckpt.load_weights(self.state.best_model_checkpoint, self.model, self.optimizer)
         self.log(metrics)
         self.control = self.callback_handler.call("on_train_end", a, self.state, self.control)
         return TrainOutput(self.state.global_step, train_loss, metrics)
