@@ -89,6 +89,12 @@ TORCH_LIBRARY(sftamd, m) {
   // loss
   // label_smoothing e in [0, 1) (HF LabelSmoother) or loss_mode 1 = dft (TRL dft_loss); stats row 0 is the objective
   m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0) -> Tensor");
+  // sequence-level objectives (csrc/preference.hip): logps[s] = -sum nll[cu[s] : cu[s + 1]]; rows of sequence s times
+  // coef[s] * gscale (rows at or past cu[n_seqs]: 0); DPO per-pair stats [5, P] = (loss, coef, reward_c, reward_r, delta)
+  m.def("seq_logp_sum(Tensor nll, Tensor cu_seqlens, int n_seqs) -> Tensor");
+  m.def("scale_rows_by_seq(Tensor x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> Tensor");
+  m.def("scale_rows_by_seq_(Tensor(a!) x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> ()");
+  m.def("dpo_pair_fwd(Tensor logps, Tensor ref_logps, Tensor inv_pairs, float beta) -> Tensor");
   // attention (window > 0: causal sliding window, query i sees keys (i - window, i]; 0: none)
   m.def("flash_fwd(Tensor qkv, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, int window=0) -> (Tensor, Tensor)");
   m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None, int window=0) -> Tensor");

@@ -1,6 +1,7 @@
 """MI355X-native distributed SFT framework (capabilities of thesteve0/llm-fine-tune-distributed).
 
-Public API mirrors the reference's TRL surface: ``SFTConfig`` + ``SFTTrainer(...).train()``.
+Public API mirrors the reference's TRL surface: ``SFTConfig`` + ``SFTTrainer(...).train()``, and for preference
+training ``DPOConfig`` + ``DPOTrainer(...).train()``.
 """
 __version__ = "0.1.0"
 
@@ -12,6 +13,12 @@ def __getattr__(name):
     if name in ("SFTConfig",):
         from .train.config import SFTConfig
         return SFTConfig
+    if name in ("DPOConfig",):
+        from .train.config import DPOConfig
+        return DPOConfig
+    if name in ("DPOTrainer",):
+        from .train.dpo import DPOTrainer
+        return DPOTrainer
     if name in ("SFTTrainer", "TrainOutput"):
         from .train import trainer
         return getattr(trainer, name)

@@ -20,16 +20,19 @@ import torch
 def main(argv=None):
     from ..data.dataset import load_jsonl, load_qa_parquet, train_test_split
     from ..data.prompts import format_prompt
-    from ..data.synthetic import generate_qa
+    from ..data.synthetic import generate_qa, synthetic_preferences
     from ..data.tokenizer import load_tokenizer
     from ..parallel.process_group import cleanup_distributed, setup_distributed
-    from ..train import (AimCallback, PerplexityCallback, SFTConfig, SFTTrainer, TrainingHistoryCallback,
-                         config_from_env)
+    from ..train import (AimCallback, DPOConfig, DPOTrainer, PerplexityCallback, SFTConfig, SFTTrainer,
+                         TrainingHistoryCallback, config_from_env)
     from ..train.config import apply_overrides
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default=os.getenv("MODEL_NAME", "HuggingFaceTB/SmolLM3-3B"),
                     help="preset name or local HF directory (config.json + safetensors)")
+    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo"],
+                    help="sft: supervised fine-tuning; dpo: preference training on {prompt, chosen, rejected} rows "
+                         "(a preference JSONL / parquet through --dataset; --set beta=...)")
     ap.add_argument("--dataset", default=os.getenv("DATASET_PATH", "data/qa_dataset.parquet"),
                     help="parquet/jsonl Q&A file; 'synthetic' (or a missing file) generates the synthetic set")
     ap.add_argument("--freeze-policy", default=os.getenv("FREEZE_POLICY", "last_n_layers"),
@@ -68,14 +71,17 @@ def main(argv=None):
     # dataset (training.py:155-212)
     if a.dataset != "synthetic" and os.path.exists(a.dataset):
         rows = load_qa_parquet(a.dataset) if a.dataset.endswith(".parquet") else load_jsonl(a.dataset)
+    elif a.trainer == "dpo":
+        rows = synthetic_preferences(2845, seed=42)
     else:
         rows = generate_qa(2845, seed=42)
         rows = [{"full-question": r["full-question"], "answer": r["answer"]} for r in rows]
     train_rows, val_rows = train_test_split(rows, test_size=0.1, seed=42)
     if st.is_main:
         print(f"Total dataset size: {len(rows):,} | train {len(train_rows):,} | val {len(val_rows):,}")
-    train_rows = [format_prompt(r) for r in train_rows]
-    val_rows = [format_prompt(r) for r in val_rows]
+    if a.trainer == "sft":
+        train_rows = [format_prompt(r) for r in train_rows]
+        val_rows = [format_prompt(r) for r in val_rows]
     tok_dir = a.model if os.path.isdir(a.model) else None
     tokenizer = load_tokenizer(tok_dir)
 
@@ -87,7 +93,8 @@ def main(argv=None):
         # full mesh the cap grows with N (parallel/ddp.py plan_bucket_mb). DDP_BUCKET_CAP_MB pins it.
         cap = float(os.environ["DDP_BUCKET_CAP_MB"]) if os.environ.get("DDP_BUCKET_CAP_MB") else None
         dist_args = dict(ddp_find_unused_parameters=False, ddp_bucket_cap_mb=cap, local_rank=st.local_rank)
-    args = SFTConfig(
+    config_cls, trainer_cls = (DPOConfig, DPOTrainer) if a.trainer == "dpo" else (SFTConfig, SFTTrainer)
+    args = config_cls(
         output_dir=f"{out}/checkpoints", per_device_train_batch_size=env["batch_size"],
         per_device_eval_batch_size=env["batch_size"], gradient_accumulation_steps=a.grad_accum,
         learning_rate=env["scaled_learning_rate"], max_grad_norm=1.0, num_train_epochs=env["epochs"],
@@ -103,7 +110,7 @@ def main(argv=None):
     args = apply_overrides(args, a.config, a.sets)
     if st.is_main:  # the resolved configuration of this run, next to its artifacts
         args.to_json(f"{out}/sft_config.json")
-    trainer = SFTTrainer(model=a.model, args=args, train_dataset=train_rows, eval_dataset=val_rows,
+    trainer = trainer_cls(model=a.model, args=args, train_dataset=train_rows, eval_dataset=val_rows,
                          processing_class=tokenizer, callbacks=[history, ppl, aim])
     if st.device.type == "cuda" and st.is_main:
         print(f"VRAM after model load: {torch.cuda.memory_allocated() / 2**30:.2f} GB allocated")

@@ -129,16 +129,24 @@ def _fingerprint(rows: Sequence[Dict], tokenizer, **kw) -> str:
 
 def cached_tokenize(rows: Sequence[Dict], tokenizer, cache_dir: Optional[str], is_main: bool = True,
                     barrier: Optional[Callable[[], None]] = None, max_length: Optional[int] = None,
-                    assistant_only_loss: bool = False, text_field: str = "text") -> TokenizedDataset:
+                    assistant_only_loss: bool = False, text_field: str = "text",
+                    tokenize: Optional[Callable] = None, fingerprint: Optional[Dict] = None) -> TokenizedDataset:
     """TRL's ``main_process_first`` tokenisation: rank 0 renders + tokenises and writes the
     CSR arrays to ``cache_dir/tokenized-<fingerprint>.pt``; the other ranks wait at ``barrier`` and load
     them. The fingerprint covers the rows, the tokenizer (vocabulary + template) and the options, so a
-    rerun with the same inputs loads instead of re-tokenising. Without ``cache_dir`` every rank tokenises."""
+    rerun with the same inputs loads instead of re-tokenising. Without ``cache_dir`` every rank tokenises.
+    Another row format goes through the same cache with ``tokenize`` (rows, tokenizer) -> TokenizedDataset and the
+    options that identify it in ``fingerprint`` (data/preference.py)."""
     import os
     kw = dict(max_length=max_length, assistant_only_loss=assistant_only_loss, text_field=text_field)
+    fp_kw = kw if tokenize is None else dict(fingerprint or {})
+
+    def run():
+        return tokenize_rows(rows, tokenizer, **kw) if tokenize is None else tokenize(rows, tokenizer)
+
     if not cache_dir:
-        return tokenize_rows(rows, tokenizer, **kw)
-    path = os.path.join(cache_dir, f"tokenized-{_fingerprint(rows, tokenizer, **kw)}.pt")
+        return run()
+    path = os.path.join(cache_dir, f"tokenized-{_fingerprint(rows, tokenizer, **fp_kw)}.pt")
 
     def load():
         d = torch.load(path, weights_only=True)
@@ -149,7 +157,7 @@ def cached_tokenize(rows: Sequence[Dict], tokenizer, cache_dir: Optional[str], i
         if os.path.exists(path):
             ds = load()
         else:
-            ds = tokenize_rows(rows, tokenizer, **kw)
+            ds = run()
             os.makedirs(cache_dir, exist_ok=True)
             tmp = f"{path}.tmp{os.getpid()}"
             torch.save({"tokens": ds.tokens, "offsets": ds.offsets, "loss_start": ds.loss_start}, tmp)
@@ -157,5 +165,5 @@ def cached_tokenize(rows: Sequence[Dict], tokenizer, cache_dir: Optional[str], i
     if barrier is not None:
         barrier()
     if ds is None:
-        ds = load() if os.path.exists(path) else tokenize_rows(rows, tokenizer, **kw)  # no shared filesystem
+        ds = load() if os.path.exists(path) else run()  # no shared filesystem
     return ds

@@ -46,6 +46,18 @@ def generate_qa(n: int = 2845, seed: int = 42) -> List[Dict[str, str]]:
     return rows
 
 
+def synthetic_preferences(n: int = 64, seed: int = 42) -> List[Dict[str, str]]:
+    """Preference rows ``{"prompt", "chosen", "rejected"}`` from the synthetic Q&A set: chosen is the row's own
+    answer, rejected the answer of another row (the next one whose answer differs)."""
+    rows = generate_qa(n, seed)
+    out = []
+    for i, r in enumerate(rows):
+        other = next((rows[(i + k) % n]["answer"] for k in range(1, n) if rows[(i + k) % n]["answer"] != r["answer"]),
+                     "I do not know.")
+        out.append({"prompt": r["full-question"], "chosen": r["answer"], "rejected": other})
+    return out
+
+
 def write_parquet(rows: List[Dict[str, str]], path: str) -> None:
     import pyarrow as pa
     import pyarrow.parquet as pq

@@ -323,7 +323,49 @@ class CausalLM(nn.Module):
         mean over valid tokens when ``num_items_in_batch`` is None. ``label_smoothing`` (HF ``LabelSmoother``) and
         ``loss_type="dft"`` (TRL ``dft_loss``) change the per-token objective inside the fused cross-entropy.
         """
-        cfg = self.config
+        dev = input_ids.device
+        h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+
+        out = CausalLMOutput()
+        if labels is not None:
+            valid = labels != -100
+            if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
+                num_items_in_batch = num_items_in_batch.resolve()
+            if num_items_in_batch is None:
+                cnt = valid.sum().clamp(min=1)
+            elif torch.is_tensor(num_items_in_batch):
+                cnt = num_items_in_batch
+            else:
+                cnt = torch.tensor(float(num_items_in_batch))
+            inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+            out.loss, out.stats = ops.lm_head_cross_entropy(h, self.lm_head_weight, labels, inv, label_smoothing,
+                                                            loss_type)
+            vf = valid.float()
+            out.num_tokens = vf.sum()
+            # TRL-style training metrics from the same fused CE pass: [correct, entropy_sum, valid]
+            out.metrics = torch.stack([out.stats[3].sum(), (out.stats[2] * vf).sum(), out.num_tokens])
+        if return_logits or labels is None:
+            out.logits = torch.nn.functional.linear(h, self.lm_head_weight)
+        return out
+
+    def sequence_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                       position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
+                       n_seqs: Optional[int] = None, shift_labels: bool = True):
+        """Per-sequence log-probabilities log pi(y | x) = sum of the label tokens' log-probabilities (-100 ignored) of
+        the first ``n_seqs`` segments of ``cu_seqlens`` (default: all of them; every row of a padded [B, T] batch).
+        Returns (logps fp32 [n_seqs], differentiable; the fused cross-entropy's stats [4, M]). The trunk is
+        ``forward``'s. Sequence-level objectives (DPO) build on this."""
+        if len(self.model.layers) and self.model.layers[0].self_attn.cp_group is not None:
+            raise NotImplementedError("sequence_logps under context parallelism: a sequence's label rows are spread "
+                                      "over the group's ranks and the per-sequence sum is not reduced across them")
+        h, labels, cu_seqlens = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+        if n_seqs is None:
+            n_seqs = cu_seqlens.numel() - 1
+        return ops.lm_head_seq_logps(h, self.lm_head_weight, labels, cu_seqlens, int(n_seqs))
+
+    def _hidden(self, input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels):
+        """The trunk shared by ``forward`` and ``sequence_logps``: batch metadata, embedding (NEFTune in training),
+        the decoder layers and the final norm. Returns (h [M, hidden], the shifted flat labels or None, cu_seqlens)."""
         dev = input_ids.device
         rope_cs = None
         padded = tuple(input_ids.shape) if input_ids.dim() == 2 and cu_seqlens is None else None
@@ -372,28 +414,7 @@ class CausalLM(nn.Module):
                     x, residual = layer(x, residual, rope_cs, cu_seqlens, max_seqlen)
         n = self.model.norm
         h, _ = ops.add_rms_norm(x, residual, n.weight, n.eps)
-
-        out = CausalLMOutput()
-        if labels is not None:
-            valid = labels != -100
-            if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
-                num_items_in_batch = num_items_in_batch.resolve()
-            if num_items_in_batch is None:
-                cnt = valid.sum().clamp(min=1)
-            elif torch.is_tensor(num_items_in_batch):
-                cnt = num_items_in_batch
-            else:
-                cnt = torch.tensor(float(num_items_in_batch))
-            inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
-            out.loss, out.stats = ops.lm_head_cross_entropy(h, self.lm_head_weight, labels, inv, label_smoothing,
-                                                            loss_type)
-            vf = valid.float()
-            out.num_tokens = vf.sum()
-            # TRL-style training metrics from the same fused CE pass: [correct, entropy_sum, valid]
-            out.metrics = torch.stack([out.stats[3].sum(), (out.stats[2] * vf).sum(), out.num_tokens])
-        if return_logits or labels is None:
-            out.logits = torch.nn.functional.linear(h, self.lm_head_weight)
-        return out
+        return h, labels, cu_seqlens
 
     # ------------------------------------------------------------------ HF state dict
     def hf_state_dict(self) -> Dict[str, torch.Tensor]:

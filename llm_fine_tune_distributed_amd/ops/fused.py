@@ -1395,6 +1395,111 @@ def lm_head_cross_entropy(h, weight, labels, inv_count, label_smoothing: float =
     return LMHeadCEFn.apply(h, weight, labels, inv_count, float(label_smoothing), LOSS_MODES[loss_type])
 
 
+# ----------------------------------------------------------------------------- sequence log-probs + DPO
+_CONSTS: dict = {}
+
+
+def _const(value: float, device) -> torch.Tensor:
+    """A cached fp32 device scalar (the unit inv_count / the -1 of the sequence-level LM head)."""
+    key = (float(value), str(device))
+    t = _CONSTS.get(key)
+    if t is None:
+        t = _CONSTS[key] = torch.full((1,), float(value), dtype=torch.float32, device=device)
+    return t
+
+
+def seq_logp_sum(nll: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int) -> torch.Tensor:
+    """logps[s] = -sum nll[cu[s] : cu[s + 1]], s < n_seqs (csrc/preference.hip; ref.seq_logp_sum)."""
+    if _ext.use_hip(nll):
+        return _ext.ops().seq_logp_sum(nll.contiguous(), cu_seqlens, int(n_seqs))
+    return ref.seq_logp_sum(nll, cu_seqlens, int(n_seqs))
+
+
+def scale_rows_by_seq(x: torch.Tensor, coef: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int,
+                      gscale: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """Row t of sequence s times coef[s] * gscale, rows past the last sequence zeroed (csrc/preference.hip; the twin
+    ref.scale_rows_by_seq is bit-equal). ``inplace`` overwrites x."""
+    if _ext.use_hip(x) and x.dtype == torch.bfloat16:
+        if inplace:
+            _ext.ops().scale_rows_by_seq_(x, coef, cu_seqlens, int(n_seqs), gscale)
+            return x
+        return _ext.ops().scale_rows_by_seq(x.contiguous(), coef, cu_seqlens, int(n_seqs), gscale)
+    out = ref.scale_rows_by_seq(x, coef, cu_seqlens, int(n_seqs), gscale)
+    return x.copy_(out) if inplace else out
+
+
+class LMHeadSeqLogpsFn(Function):
+    """logps[s] = sum over the rows t of sequence s of log softmax(h_t W^T)[y_t] (ignored rows add 0). As in LMHeadCEFn
+    the forward leaves G = softmax - onehot over the logits; the backward's per-sequence weight r_s = -dlogps[s] goes
+    onto the two [T, hidden] operands (dh = diag(r) (G W), dW = G^T (diag(r) h)), never onto the [T, vocab] one."""
+
+    @staticmethod
+    def forward(ctx, h, weight, labels, cu_seqlens, n_seqs):
+        h2d = h.reshape(-1, h.shape[-1])
+        logits = fwd_gemm(h2d, weight) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, weight)
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        stats = _ce_rows(logits, labels.reshape(-1), _const(1.0, h.device), need_grad)
+        logps = seq_logp_sum(stats[0], cu_seqlens, n_seqs)
+        if need_grad:
+            ctx.save_for_backward(h2d, logits, cu_seqlens)
+        ctx.weight = weight
+        ctx.h_shape = h.shape
+        ctx.n_seqs = int(n_seqs)
+        ctx.mark_non_differentiable(stats)
+        return logps, stats
+
+    @staticmethod
+    def backward(ctx, dlogps, _dstats):
+        h2d, G, cu = ctx.saved_tensors
+        w, n = ctx.weight, ctx.n_seqs
+        coef = dlogps.float().contiguous()
+        neg = _const(-1.0, h2d.device)  # r = -dlogps: coef * gscale, one product
+        dh = dw = None
+        if ctx.needs_input_grad[0]:
+            dh = scale_rows_by_seq(dgrad_mm(G, w), coef, cu, n, neg, inplace=True).view(ctx.h_shape)
+        if ctx.needs_input_grad[1]:
+            # (out of place: h2d is a saved activation)
+            dw = _accumulate_weight_grad(w, G, scale_rows_by_seq(h2d, coef, cu, n, neg))
+        return dh, dw, None, None, None
+
+
+def lm_head_seq_logps(h, weight, labels, cu_seqlens, n_seqs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-sequence log-probabilities of ``labels`` (already shifted, -100 ignored) under the LM head: differentiable
+    ``logps`` [n_seqs] (fp32 on the bf16 path) and the fused cross-entropy's stats [4, M]."""
+    if cu_seqlens.numel() < int(n_seqs) + 1:
+        raise ValueError(f"n_seqs {n_seqs} over the {cu_seqlens.numel() - 1} segments of cu_seqlens")
+    return LMHeadSeqLogpsFn.apply(h, weight, labels, cu_seqlens, int(n_seqs))
+
+
+def dpo_pair_stats(logps, ref_logps, inv_pairs, beta: float) -> torch.Tensor:
+    """stats [5, P] = (loss, coef, reward_chosen, reward_rejected, delta) of P pairs (csrc/preference.hip)."""
+    if _ext.use_hip(logps) and logps.dtype == torch.float32:
+        return _ext.ops().dpo_pair_fwd(logps.contiguous(), ref_logps.float().contiguous(), inv_pairs, float(beta))
+    return ref.dpo_pair(logps, ref_logps, inv_pairs, float(beta))
+
+
+class DPOLossFn(Function):
+    @staticmethod
+    def forward(ctx, logps, ref_logps, inv_pairs, beta):
+        stats = dpo_pair_stats(logps, ref_logps, inv_pairs, beta)
+        ctx.save_for_backward(stats[1])
+        ctx.mark_non_differentiable(stats)
+        return (stats[0].sum() * inv_pairs.to(stats.dtype).reshape(())).reshape(()), stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        coef, = ctx.saved_tensors
+        return torch.stack([coef, -coef], dim=1).reshape(-1) * dloss, None, None, None
+
+
+def dpo_loss(logps, ref_logps, inv_pairs, beta: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """DPO sigmoid loss of P pairs (sequence 2p chosen, 2p + 1 rejected): loss = inv_pairs * sum softplus(-beta
+    delta_p), and the per-pair stats [5, P]. ``inv_pairs`` is a fp32 scalar tensor on logps' device."""
+    if logps.dim() != 1 or logps.numel() % 2 or ref_logps.shape != logps.shape:
+        raise ValueError(f"dpo_loss: logps / ref_logps must be [2 P], got {tuple(logps.shape)} / {tuple(ref_logps.shape)}")
+    return DPOLossFn.apply(logps, ref_logps, inv_pairs, float(beta))
+
+
 # ----------------------------------------------------------------------------- LoRA linear
 class LoRALinearFn(Function):
     """y = x W^T + scaling * concat_i(dropout(x) A_i^T B_i^T) over the sub-projections of a fused

@@ -323,3 +323,51 @@ def lora_bwd_dx(base: torch.Tensor, dxa: torch.Tensor, A: torch.Tensor, p: float
     if p > 0:
         return dropout_add(base, dxd, p, seed)
     return (base.float() + dxd.float()).to(base.dtype)
+
+
+# ----------------------------------------------------------------------------- sequence-level objectives (DPO)
+def _row_segments(M: int, cu_seqlens: torch.Tensor, n_seqs: int) -> torch.Tensor:
+    """int64 [M]: the segment of ``cu_seqlens`` each row lies in; ``n_seqs`` for rows at or past ``cu[n_seqs]``."""
+    t = torch.arange(M, dtype=torch.int64, device=cu_seqlens.device)
+    return torch.searchsorted(cu_seqlens[1:n_seqs + 1].to(torch.int64).contiguous(), t, right=True)
+
+
+def seq_logp_sum(nll: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int) -> torch.Tensor:
+    """logps[s] = -sum nll[cu[s] : cu[s + 1]] for the first ``n_seqs`` segments (an empty one gives 0; later segments,
+    the collator's pad, are ignored) — twin of csrc/preference.hip seq_logp_sum, in nll's dtype."""
+    seg = _row_segments(nll.numel(), cu_seqlens.to(nll.device), n_seqs)
+    keep = seg < n_seqs
+    out = torch.zeros(n_seqs, dtype=nll.dtype, device=nll.device)
+    return out.index_add_(0, seg[keep], -nll[keep])
+
+
+def scale_rows_by_seq(x: torch.Tensor, coef: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int,
+                      gscale: torch.Tensor) -> torch.Tensor:
+    """out[t, :] = x[t, :] * (coef[s(t)] * gscale) with s(t) the segment of row t, +0 on rows at or past ``cu[n_seqs]``.
+    Bit-equal to csrc/preference.hip scale_rows_by_seq on bf16: the two scalars are multiplied first, in fp32, then
+    one fp32 product per element and one rounding to x's dtype (fp64 stays fp64)."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    M = x.shape[0]
+    if n_seqs == 0 or M == 0:
+        return torch.zeros_like(x)
+    seg = _row_segments(M, cu_seqlens.to(x.device), n_seqs)
+    c = coef.to(ct) * gscale.to(ct).reshape(())
+    rows = c[seg.clamp(max=n_seqs - 1)]
+    out = (x.to(ct) * rows[:, None]).to(x.dtype)
+    return torch.where((seg >= n_seqs)[:, None], torch.zeros((), dtype=x.dtype, device=x.device), out)
+
+
+def dpo_pair(logps: torch.Tensor, ref_logps: torch.Tensor, inv_pairs: torch.Tensor, beta: float) -> torch.Tensor:
+    """DPO (sigmoid loss) per pair, sequence 2p chosen and 2p + 1 rejected — twin of csrc/preference.hip dpo_pair_fwd.
+    stats [5, P] in logps' dtype: loss = softplus(-beta delta) as max(-z, 0) + log1p(exp(-|z|)), coef = d(inv_pairs
+    sum loss) / d logp_chosen = -beta sigmoid(-z) inv_pairs (the rejected sequence's is its negative), reward_chosen,
+    reward_rejected, delta = (pi_c - pi_r) - (ref_c - ref_r)."""
+    ref_logps = ref_logps.to(logps.dtype)
+    pc, pr, rc, rr = logps[0::2], logps[1::2], ref_logps[0::2], ref_logps[1::2]
+    delta = (pc - pr) - (rc - rr)
+    z = beta * delta
+    e = torch.exp(-z.abs())
+    loss = (-z).clamp(min=0) + torch.log1p(e)
+    sig = torch.where(z >= 0, e, torch.ones_like(e)) / (1 + e)
+    coef = (-beta * sig) * inv_pairs.to(logps.dtype).reshape(())
+    return torch.stack([loss, coef, beta * (pc - rc), beta * (pr - rr), delta])

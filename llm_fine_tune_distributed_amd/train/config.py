@@ -205,7 +205,7 @@ class SFTConfig:
         """Copy with ``overrides`` applied (same alias / unknown-field handling as the constructor)."""
         kw = self.to_dict()
         kw.update(overrides)
-        return SFTConfig(**kw)
+        return type(self)(**kw)
 
 
 def _coerce(field_type, raw: str):
@@ -250,7 +250,7 @@ def apply_overrides(cfg: SFTConfig, config_file: Optional[str] = None,
                     sets: Optional[List[str]] = None) -> SFTConfig:
     """Layering (lowest to highest): ``cfg`` (code defaults + env contract) < config file < ``--set k=v``.
     Unknown keys raise here (a typo in a config file must not be silently ignored)."""
-    fields = {f.name: f.type for f in dataclasses.fields(SFTConfig)}
+    fields = {f.name: f.type for f in dataclasses.fields(type(cfg))}  # (DPOConfig adds its own)
     aliases = {"max_seq_length": "max_length", "evaluation_strategy": "eval_strategy"}
     over: Dict[str, Any] = {}
     if config_file:
@@ -287,6 +287,56 @@ def _init(self, *args, **kw):
 
 
 SFTConfig.__init__ = _init
+
+
+@dataclass
+class DPOConfig(SFTConfig):
+    """``SFTConfig`` plus TRL's ``DPOConfig`` fields for preference training (train/dpo.py). Reference log-probs are
+    always precomputed (TRL ``precompute_ref_log_probs=True``); batches are always padding-free."""
+    learning_rate: float = 1e-6             # TRL DPOConfig's default
+    loss_type: str = "sigmoid"              # the DPO paper's loss; the only one implemented
+    beta: float = 0.1
+    max_prompt_length: Optional[int] = None  # prompts longer than this keep their last tokens
+
+    def __post_init__(self):
+        self.validate_objective()
+
+    def validate_objective(self) -> None:
+        a = self.neftune_noise_alpha
+        if a is not None and not float(a) >= 0:
+            raise ValueError(f"neftune_noise_alpha must be None or >= 0, got {a}")
+        if self.loss_type != "sigmoid":
+            raise ValueError(f"DPOConfig: loss_type must be 'sigmoid', got {self.loss_type!r}")
+        if float(self.label_smoothing_factor) != 0.0:
+            raise ValueError("DPOConfig: label_smoothing_factor is a per-token option (cDPO smoothing is not "
+                             "implemented)")
+        if self.packing:
+            raise ValueError("DPOConfig: packing=True is not supported (batches of pairs are padding-free already)")
+        if int(self.context_parallel_size or 1) > 1:
+            raise ValueError("DPOConfig: context_parallel_size > 1 is not supported (per-sequence log-probabilities "
+                             "are not reduced across a context-parallel group)")
+        if not float(self.beta) > 0:
+            raise ValueError(f"DPOConfig: beta must be > 0, got {self.beta}")
+        if self.max_prompt_length is not None and int(self.max_prompt_length) < 1:
+            raise ValueError(f"DPOConfig: max_prompt_length must be None or >= 1, got {self.max_prompt_length}")
+
+
+def _tolerant_init(cls_init):
+    """The same legacy-alias / unknown-field handling as SFTConfig's constructor, for a subclass's own __init__."""
+    def init(self, *args, **kw):
+        names = {f.name for f in dataclasses.fields(type(self))}
+        if "max_seq_length" in kw:
+            kw["max_length"] = kw.pop("max_seq_length")
+        if "evaluation_strategy" in kw:
+            kw["eval_strategy"] = kw.pop("evaluation_strategy")
+        unknown = {k: kw.pop(k) for k in list(kw) if k not in names}
+        if unknown:
+            warnings.warn(f"{type(self).__name__}: ignoring unsupported fields {sorted(unknown)}")
+        cls_init(self, *args, **kw)
+    return init
+
+
+DPOConfig.__init__ = _tolerant_init(DPOConfig.__init__)
 
 
 def config_from_env(base: Optional[SFTConfig] = None, world_size: int = 1) -> Dict[str, Any]:

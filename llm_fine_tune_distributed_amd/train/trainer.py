@@ -344,6 +344,33 @@ class SFTTrainer:
                        labels=torch.cat([F.pad(b["labels"], (0, T - b["labels"].shape[1]), value=-100) for b in micro]))
         return [out]
 
+    # ---- the objective's seams (DPOTrainer overrides them; the loops below are shared)
+    _acc_size = 4  # the running accumulator of a step / a log window: loss, then the objective's metric sums
+
+    def _micro_loss(self, b: Dict, n_items):
+        """(loss of one micro-batch, normalised by the step's global count ``n_items``; its metric sums
+        [_acc_size - 1]): what the step back-propagates and what the accumulator adds."""
+        out = self.model(**self._model_inputs(b), num_items_in_batch=n_items, **self._objective())
+        return out.loss, out.metrics
+
+    def _eval_loss(self, b: Dict):
+        """(summed loss of one evaluation batch, its metric sums [_acc_size - 1])."""
+        out = self.model(**self._model_inputs(b), num_items_in_batch=1.0, **self._objective())
+        return out.loss, out.metrics
+
+    def _train_logs(self, v: List[float], steps: int, common: Dict[str, Any]) -> Dict[str, Any]:
+        """The log entry of a window of ``steps`` optimizer steps from the all-reduced accumulator ``v``."""
+        valid = max(v[3], 1.0)
+        return {"loss": v[0] / steps, "grad_norm": common["grad_norm"], "learning_rate": common["learning_rate"],
+                "epoch": common["epoch"], "mean_token_accuracy": v[1] / valid, "entropy": v[2] / valid,
+                "num_tokens": common["num_tokens"]}
+
+    def _eval_logs(self, v: List[float], prefix: str, common: Dict[str, Any]) -> Dict[str, Any]:
+        """The evaluation metrics from the all-reduced accumulator ``v`` (its last entry: samples) and the rates."""
+        valid = max(v[3], 1.0)
+        return {f"{prefix}_loss": v[0] / valid, **common, f"{prefix}_mean_token_accuracy": v[1] / valid,
+                f"{prefix}_entropy": v[2] / valid, f"{prefix}_num_tokens": v[3]}
+
     def optimizer_step(self, micro: List[Dict], lr: float) -> Dict[str, torch.Tensor]:
         """One optimizer step over ``micro`` (GA micro-batches). Returns device-side sums:
         loss (this rank's share of the global mean), correct, entropy_sum, valid tokens."""
@@ -356,7 +383,7 @@ class SFTTrainer:
         beat = self.heartbeat.beat
         micro = self._merge_micro([self._cp_shard(b) for b in micro])
         n_items = self.global_num_items(micro)
-        acc = torch.zeros(4, device=self.dist.device)  # loss, correct, entropy_sum, valid
+        acc = torch.zeros(self._acc_size, device=self.dist.device)  # SFT: loss, correct, entropy_sum, valid
         for i, b in enumerate(micro):
             sync = i == len(micro) - 1
             ctx = contextlib.nullcontext() if sync else eng.no_sync()
@@ -364,12 +391,12 @@ class SFTTrainer:
                 eng.prepare_backward()
                 beat(self._hb_step, "fwd", micro=i)
                 with self._phase("fwd"):
-                    out = model(**self._model_inputs(b), num_items_in_batch=n_items, **self._objective())
+                    loss, metrics = self._micro_loss(b, n_items)
                 beat(self._hb_step, "bwd", micro=i)
                 with self._phase("bwd"):
-                    out.loss.backward()
-            acc[0] += out.loss.detach()
-            acc[1:] += out.metrics
+                    loss.backward()
+            acc[0] += loss.detach()
+            acc[1:] += metrics
         beat(self._hb_step, "comm_wait")
         with self._phase("comm_wait"):
             eng.finish_backward()
@@ -389,28 +416,26 @@ class SFTTrainer:
         t0 = time.time()
         self.optimizer.synchronize()
         self.model.eval()
-        acc = torch.zeros(5, device=self.dist.device)  # loss_sum, correct, entropy_sum, valid, samples
+        n = self._acc_size
+        acc = torch.zeros(n + 1, device=self.dist.device)  # SFT: loss_sum, correct, entropy_sum, valid; then samples
         loader = self.get_eval_dataloader()
         beat = self.heartbeat.beat
         for b in loader:
             beat(self._hb_step, "eval")
             b = self._cp_shard(b)
-            out = self.model(**self._model_inputs(b), num_items_in_batch=1.0, **self._objective())
-            acc[0] += out.loss
-            acc[1:4] += out.metrics
-            acc[4] += b["num_samples"] if self.cp_rank == 0 else 0  # a CP group shares its samples
+            loss, metrics = self._eval_loss(b)
+            acc[0] += loss
+            acc[1:n] += metrics
+            acc[n] += b["num_samples"] if self.cp_rank == 0 else 0  # a CP group shares its samples
         all_reduce_sum_(acc)
         vals = acc.tolist()
         self.model.train()
         rt = time.time() - t0
-        valid = max(vals[3], 1.0)
         nb = len(loader) * self.dp_size
-        m = {f"{metric_key_prefix}_loss": vals[0] / valid, f"{metric_key_prefix}_runtime": rt,
-             f"{metric_key_prefix}_samples_per_second": vals[4] / max(rt, 1e-9),
-             f"{metric_key_prefix}_steps_per_second": nb / max(rt, 1e-9),
-             f"{metric_key_prefix}_mean_token_accuracy": vals[1] / valid,
-             f"{metric_key_prefix}_entropy": vals[2] / valid, f"{metric_key_prefix}_num_tokens": vals[3],
-             "epoch": self.state.epoch}
+        m = self._eval_logs(vals, metric_key_prefix, {f"{metric_key_prefix}_runtime": rt,
+                                                      f"{metric_key_prefix}_samples_per_second": vals[n] / max(rt, 1e-9),
+                                                      f"{metric_key_prefix}_steps_per_second": nb / max(rt, 1e-9)})
+        m["epoch"] = self.state.epoch
         self._timers["eval"] += rt
         self.callback_handler.call("on_evaluate", self.args, self.state, self.control, metrics=m)
         self.log(m)
@@ -528,7 +553,7 @@ class SFTTrainer:
         log_every = max(1, int(a.logging_steps)) if a.logging_steps else 0
         save_every = int(a.save_steps) if a.save_strategy == "steps" and a.save_steps else 0
         cfg = self.model.config
-        run_acc = torch.zeros(4, device=self.dist.device)
+        run_acc = torch.zeros(self._acc_size, device=self.dist.device)
         steps_since_log = 0
         total_loss = torch.zeros(1, device=self.dist.device)
         samples = tokens = 0
@@ -587,11 +612,9 @@ class SFTTrainer:
                     red = run_acc.clone()
                     all_reduce_sum_(red)
                     v = red.tolist()
-                    valid = max(v[3], 1.0)
-                    logs = {"loss": v[0] / steps_since_log, "grad_norm": float(last_norm),
-                            "learning_rate": self.scheduler.get_lr(), "epoch": round(self.state.epoch, 4),
-                            "mean_token_accuracy": v[1] / valid, "entropy": v[2] / valid,
-                            "num_tokens": float(self.state.tokens_seen)}
+                    logs = self._train_logs(v, steps_since_log, {
+                        "grad_norm": float(last_norm), "learning_rate": self.scheduler.get_lr(),
+                        "epoch": round(self.state.epoch, 4), "num_tokens": float(self.state.tokens_seen)})
                     if self.dist.device.type == "cuda":
                         logs["hbm_peak_gb"] = round(torch.cuda.max_memory_allocated(self.dist.device) / 1e9, 3)
                         if self.dist.world_size > 1:
