@@ -457,6 +457,21 @@ static void launch(const u16* A, long lda, const u16* B, long ldb, int M, int N,
   launch2<LA, LB>(q, q, tiles, tiles, kred, ndp, splits);
 }
 
+// Op32 keeps its reduction progress (koff, kst, jst, kmax) as 32-bit byte offsets from the tile's descriptor base, and
+// the descriptor is unbounded: an offset past 2^32 wraps to an earlier row of the operand and the kernel returns a
+// wrong sum without a fault. The launchers below therefore refuse any operand whose offsets could reach 2^32 bytes.
+// TR operand: the last piece of the last step ends below rows * pitch * 2 bytes from the tile's base.
+static void check_tr_span(const char* op, const char* operand, long rows, long pitch) {
+  SFT_CHECK(rows * pitch * 2 < (1L << 32), op, ": 32-bit addressing: operand ", operand, " spans ", rows,
+            " reduction rows of pitch ", pitch, " (", rows * pitch * 2,
+            " bytes >= 2^32); use a pointer-advancing ring");
+}
+// ROW operand: 256 tile rows of `pitch` elements plus the reduction length along the row.
+static void check_row_span(const char* op, const char* operand, long pitch, long kred) {
+  SFT_CHECK(256 * pitch * 2 + kred * 2 < (1L << 32), op, ": 32-bit addressing: operand ", operand, " has row pitch ",
+            pitch, " and reduction length ", kred, " (a 256-row tile spans >= 2^32 bytes)");
+}
+
 }  // namespace g4
 
 // Weight gradient out[N, K] (+)= dy[T, N]^T x[T, K] on the 4-wave kernel. splits > 1: the tiles past the last whole
@@ -468,6 +483,8 @@ void g4_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& out, bool a
   SFT_CHECK(N % 256 == 0 && K % 256 == 0 && T % 128 == 0 && T > 0, "wgrad 4-wave: N, K % 256, T % 128");
   SFT_CHECK((uintptr_t)dy.data_ptr() % 16 == 0 && (uintptr_t)x.data_ptr() % 16 == 0 &&
                 (uintptr_t)out.data_ptr() % 16 == 0, "wgrad 4-wave: 16-byte aligned operands");
+  g4::check_tr_span("wgrad 4-wave", "dy", T, std::max<long>(dy.stride(0), N));
+  g4::check_tr_span("wgrad 4-wave", "x", T, x.stride(0));
   const int tiles = (N / 256) * (K / 256);
   if (splits < 1) splits = 1;
   splits = std::min(splits, T / 128);
@@ -514,6 +531,8 @@ void g4_wgrad_multi(const std::vector<WgradJob>& jobs, int split_all, int split_
     SFT_CHECK((uintptr_t)j.dy.data_ptr() % 16 == 0 && (uintptr_t)j.x.data_ptr() % 16 == 0 &&
                   (uintptr_t)j.out.data_ptr() % 16 == 0,
               "wgrad multi: 16-byte aligned operands");
+    g4::check_tr_span("wgrad multi", "dy", T, std::max<long>(j.dy.stride(0), N));
+    g4::check_tr_span("wgrad multi", "x", T, j.x.stride(0));
     tiles[i] = (N / 256) * (K / 256);
     start[i + 1] = start[i] + tiles[i];
   }
@@ -597,6 +616,8 @@ void g4_dgrad(const at::Tensor& dy, const at::Tensor& w, u16* out, long ldo, con
               float* delta) {
   const int M = dy.size(0), K = dy.size(1), N = w.size(1);
   SFT_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K > 0, "dgrad 4-wave: M, N % 256, K % 128");
+  g4::check_row_span("dgrad 4-wave", "dy", dy.stride(0), K);
+  g4::check_tr_span("dgrad 4-wave", "w", K, w.stride(0));
   g4::Epi ea{};
   ea.C = out;
   ea.ldc = ldo;

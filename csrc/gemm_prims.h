@@ -26,7 +26,9 @@ __device__ __forceinline__ void glds16(const u16* src, char* dst) {
 // VGPR fixed for the whole loop, the piece / K-step offset in an SGPR — no per-piece 64-bit VALU address arithmetic
 // (the global_load_lds form costs a v_lshl_add_u64 per piece), as hipBLASLt's MT256x256x64 loop does.
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t tile_rsrc(const u16* p) {  // unbounded range: the caller keeps its offsets in bounds
+// Unbounded range, 32-bit offsets: the HOST launchers check that no offset of a launch can reach 2^32 bytes
+// (csrc/gemm_4w.hip check_tr_span / check_row_span, csrc/gemm_tn.hip launch6); the kernels themselves do not.
+__device__ __forceinline__ rsrc_t tile_rsrc(const u16* p) {
   const unsigned long long a = (unsigned long long)p;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0xFFFFFFFFu, 0x00020000);

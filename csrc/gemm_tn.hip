@@ -930,6 +930,10 @@ void launch6(const at::Tensor& a, const at::Tensor& w, int N, const EpiArgs& ea,
   auto A = (const u16*)a.data_ptr();
   auto B = (const u16*)w.data_ptr();
   const long lda = a.stride(0), ldb = w.stride(0);
+  // Stager5 addresses the WHOLE weight from one descriptor and an A tile's 256 rows from another, in 32-bit bytes
+  SFT_CHECK((long)N * ldb * 2 + (long)K * 2 < (1L << 32) && 256 * lda * 2 + (long)K * 2 < (1L << 32),
+            "gemm_tn cfg 60 / 61: 32-bit addressing: the weight (", N, " rows of pitch ", ldb,
+            ") or a 256-row tile of a (pitch ", lda, ") spans >= 2^32 bytes");
   if (K == 128) {
     if (nt) tn6_kernel<EPI, true, 2><<<grid, 256, 0, cur_stream()>>>(A, B, K, lda, ldb, nbm, nbn, grp, ea);
     else tn6_kernel<EPI, true, 0><<<grid, 256, 0, cur_stream()>>>(A, B, K, lda, ldb, nbm, nbn, grp, ea);

@@ -76,7 +76,16 @@ def cu_budget() -> int:
     return _CU_BUDGET
 
 
-def _wgrad_cfg(T: int, N: int, K: int) -> int:
+_G4_SPAN = 1 << 32  # bytes the 4-wave ring (csrc/gemm_4w.hip Op32) addresses from a tile's base: 32-bit offsets
+
+
+def _g4_tr_fits(rows: int, *pitches: int) -> bool:
+    """Whether operands walked ``rows`` deep along the reduction at these row pitches (bf16 elements) stay inside the
+    4-wave ring's 32-bit byte offsets; its launchers raise otherwise (csrc/gemm_4w.hip check_tr_span)."""
+    return rows * max(pitches) * 2 < _G4_SPAN
+
+
+def _wgrad_cfg(T: int, N: int, K: int, ld_dy: Optional[int] = None, ld_x: Optional[int] = None) -> int:
     """Which wgrad GEMM runs dW[N,K] = dy[T,N]^T x[T,K]: 0 = hipBLASLt/rocBLAS, else a csrc/gemm_wgrad.hip cfg
     (1000 H + 100 S + c). From interleaved A/Bs on MI355X at T = 8192 (tools/bench_ab.py, profiles/r6_gemm_routing.md):
     the 4-wave ring with one read / DMA piece per MFMA gap (c = 14, csrc/gemm_4w.hip) on every shape with N, K % 256 and
@@ -84,14 +93,18 @@ def _wgrad_cfg(T: int, N: int, K: int) -> int:
     pair-loop kernel; o_proj 64 tiles x 4: 0.0705 vs 0.0715 for the 8-wave 256 x 128 ring split 2), grids whose last
     round is partial hybrid-split (down_proj 344 tiles: 0.274 vs 0.310 unsplit; lm_head 4008: 2.969 vs 3.237 for the
     8-wave 256 x 256 ring), gate_up (688 tiles) unsplit (0.534 vs 0.575 hybrid). Stream-K over the last round was
-    no faster on any of them. The 8-wave rings (c = 9 / 10) remain for K % 256 != 0 or T % 128 != 0."""
+    no faster on any of them. The 8-wave rings (c = 9 / 10) remain for K % 256 != 0 or T % 128 != 0, and for operands
+    whose token axis spans 2^32 bytes or more (T x row pitch x 2, ``ld_dy`` / ``ld_x`` = the pitches, default N / K):
+    the 4-wave ring keeps its reduction progress in 32-bit byte offsets and refuses them, the 8-wave rings advance
+    64-bit pointers. With the vocabulary 128256 that is the lm_head from T = 16744 on: cfg 10, 3.237 vs 2.969 ms by the
+    T = 8192 figures above (not measured at that T)."""
     if _WGRAD_MODE == "blas" or T % 32 or T < 1024:
         return 0
     if _WGRAD_MODE not in ("auto", ""):
         return int(_WGRAD_MODE)
     tiles = (N // 256) * (K // 256)
     B = _CU_BUDGET  # one round of workgroups (256 unless collectives hold CUs: set_cu_budget)
-    if N % 256 == 0 and K % 256 == 0 and T % 128 == 0:
+    if N % 256 == 0 and K % 256 == 0 and T % 128 == 0 and _g4_tr_fits(T, ld_dy or N, ld_x or K):
         if tiles < B:
             s = min(8, B // tiles, T // 128)
             return 100 * s + 14 if s >= 2 else 14
@@ -116,12 +129,14 @@ def _wgrad_mm(out: torch.Tensor, dy2d: torch.Tensor, x2d: torch.Tensor, accumula
     slots the ring kernels fill with the sum of squares of the values they store; returns whether they did
     (other variants leave the norm to DDPEngine.grad_norm_sq's leftover pass)."""
     cfg = 0
+    # the 4-wave kernel reads x through its row pitch (a padded [T, K] view, e.g. the gate_up input); others copy
+    x_rows = x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.data_ptr() % 16 == 0
     if _ext.use_hip(dy2d) and dy2d.dtype == torch.bfloat16 and out.is_contiguous():
-        cfg = _wgrad_cfg(dy2d.shape[0], dy2d.shape[1], x2d.shape[1])
+        # dy goes in contiguous (pitch N); x at its own pitch when the 4-wave kernel can read it in place
+        cfg = _wgrad_cfg(dy2d.shape[0], dy2d.shape[1], x2d.shape[1], ld_x=x2d.stride(0) if x_rows else None)
     if cfg:
         use_norm = norm is not None and cfg % 100 in (9, 10, 14)
-        # the 4-wave kernel reads x through its row pitch (a padded [T, K] view, e.g. the gate_up input); others copy
-        strided_ok = cfg % 100 == 14 and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.data_ptr() % 16 == 0
+        strided_ok = cfg % 100 == 14 and x_rows
         _ext.ops().wgrad_gemm(out, dy2d.contiguous(), x2d if strided_ok else x2d.contiguous(), accumulate, cfg,
                               norm if use_norm else None)
         return use_norm
@@ -178,13 +193,14 @@ _WGRAD_PAIR = os.environ.get("SFTAMD_WGRAD_PAIR", "1") == "1"
 
 def _job_tiles(p, dy, x) -> Optional[int]:
     """The 256 x 256 tile count of a weight gradient the 4-wave multi-problem launches take (HIP path, bf16 main_grad,
-    256-multiple shapes, aligned rows); None for any other job, which always launches on its own."""
+    256-multiple shapes, aligned rows, token axis inside the kernel's 32-bit offsets: _g4_tr_fits); None for any other
+    job, which always launches on its own."""
     mg = getattr(p, "main_grad", None)
     if not (dy.is_cuda and _ext.use_hip(dy) and x.shape[0] == dy.shape[0]
             and mg is not None and mg.dtype == torch.bfloat16 and mg.is_contiguous() and dy.dtype == torch.bfloat16
             and x.dtype == torch.bfloat16 and dy.shape[1] % 256 == 0 and x.shape[1] % 256 == 0
             and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
-            and mg.data_ptr() % 16 == 0):
+            and mg.data_ptr() % 16 == 0 and _g4_tr_fits(dy.shape[0], dy.shape[1], x.stride(0))):
         return None
     return (dy.shape[1] // 256) * (x.shape[1] // 256)
 
@@ -661,18 +677,22 @@ def _ring8_rounds(M: int, N: int) -> bool:
     return (nbn - main_n) * (M // 128) <= _NUM_CUS
 
 
-def _dgrad_cfg(dy2d: torch.Tensor, swiglu: bool = False, N: Optional[int] = None) -> int:
+def _dgrad_cfg(dy2d: torch.Tensor, swiglu: bool = False, N: Optional[int] = None, ld_w: Optional[int] = None) -> int:
     """Kernel configuration (csrc/gemm_dgrad.hip). 5 = the 8-wave 32-deep three-stage ring, 7 = its 64-deep
     two-stage sibling, both with conflict-free natural-order transposed reads; 14 = the 4-wave ring of
     csrc/gemm_4w.hip (one read / DMA piece per MFMA gap, split-K for a partial last round).
     M = 8192 (profiles/r6_gemm_routing.md, interleaved, ms): SwiGLU-fused down 0.400 (5) vs 0.409 (7) vs 0.483
     (4-wave register epilogue); plain gate_up 0.535 (5) vs 0.546 (14), down 0.289 vs 0.297, qkv 0.0789 vs 0.0788,
     o 0.058 vs 0.0597, lm_head 3.11 vs 3.04 -> cfg 5 when its grid is whole rounds (or the wave tail applies) and
-    the reduction is not vocabulary-long, cfg 14 otherwise (ragged token counts: its split-K tail)."""
+    the reduction is not vocabulary-long, cfg 14 otherwise (ragged token counts: its split-K tail). cfg 14 addresses
+    in 32-bit byte offsets (csrc/gemm_4w.hip check_row_span / check_tr_span): a 256-row tile of dy and the K rows of
+    the weight (row pitch ``ld_w``, default N) must each span less than 2^32 bytes, else the 8-wave rings take it."""
     K = dy2d.shape[1]
     if swiglu:
         return 5
-    if K % 128 == 0:
+    g4_fits = (256 * dy2d.stride(0) * 2 + K * 2 < _G4_SPAN
+               and (N is None and ld_w is None or _g4_tr_fits(K, ld_w or N)))
+    if K % 128 == 0 and g4_fits:
         if (_DGRAD_RING8 and N is not None and K < 65536 and _ring8_rounds(dy2d.shape[0], N)):
             return 5
         return 14
@@ -685,7 +705,7 @@ def dgrad_mm(dy2d: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     _dgrad_cfg); reductions that are not a multiple of 128 of at most 4096 output features into at most 4096 inputs
     on cfg 7 / 5."""
     if _dgrad_ok(dy2d, w):
-        cfg = _dgrad_cfg(dy2d, N=w.shape[1])
+        cfg = _dgrad_cfg(dy2d, N=w.shape[1], ld_w=w.stride(0))
         if dy2d.shape[1] % 128 == 0 or _DGRAD_MODE == "hip" or (dy2d.shape[1] <= 4096 and w.shape[1] <= 4096):
             return _ext.ops().dgrad_gemm(dy2d, w, None, cfg)
     return torch.mm(dy2d, w)

@@ -5,6 +5,7 @@ row by the square root of the number of tiles: a 32 x 32 block of a 4096 x 4096 
 moves the global error from 1.66e-3 to 1.91e-3 (tests/test_blockwise_cpu.py). The functions here judge every
 ``br x bc`` block on its own, and build small-integer operands on which a GEMM with fp32 accumulation and one
 round-to-nearest-even store has exactly one right answer."""
+import contextlib
 import math
 
 import torch
@@ -110,3 +111,40 @@ def swiglu_bwd_reference(dact64: torch.Tensor, gu: torch.Tensor, br: int = 32, b
     want = torch.cat(swiglu_bwd_expr(dact64, g, u), dim=-1)
     emul = torch.cat(swiglu_bwd_expr(dact64.float(), g.float(), u.float()), dim=-1).to(torch.bfloat16)
     return want, 2 * block_rel_err(emul, want, br, bc).max().item()
+
+
+# ------------------------------------------------------------------ exact comparison and the dispatch trace
+@contextlib.contextmanager
+def traced():
+    """Collects the dispatch trace of the launches inside the block: ``box`` maps kernel-route names to counts."""
+    from llm_fine_tune_distributed_amd.ops import _ext
+    ops, box = _ext.ops(), {}
+    ops.dispatch_trace(True)
+    try:
+        yield box
+    finally:
+        ops.dispatch_trace(False)
+        box.update(kv.split("=") for kv in ops.dispatch_trace_read().split(";") if kv)
+
+
+def exact(a32: torch.Tensor) -> torch.Tensor:
+    """bf16 of an exact fp32 integer result (the one rounding the kernel may make)."""
+    assert a32.dtype == torch.float32 and a32.abs().max().item() < 2 ** 24
+    return a32.to(torch.bfloat16)
+
+
+def mismatch(out, want):
+    """Where two tensors differ, for the assertion message: count, first index, the 256 x 256 tiles touched."""
+    bad = (out != want).nonzero()
+    if bad.numel() == 0:
+        return "equal"
+    tiles = torch.unique(bad // 256, dim=0)
+    first = tuple(bad[0].tolist())
+    return (f"{bad.shape[0]} of {out.numel()} elements differ, first at {list(first)} "
+            f"(got {out[first].item()}, want {want[first].item()}), "
+            f"{tiles.shape[0]} 256x256 tiles touched, e.g. {tiles[:4].tolist()}")
+
+
+def assert_exact(out, want, what=""):
+    assert out.shape == want.shape and out.dtype == want.dtype, (what, out.shape, want.shape)
+    assert torch.equal(out, want), (what, mismatch(out, want))

@@ -35,11 +35,18 @@ def _first_max(x):
 def _check(logits, labels, write_grad):
     """One ce_fwd call on a copy of ``logits``; every row of loss, lse, entropy, correct and the gradient against
     fp64. Returns the measured maxima (loss / lse absolute error, gradient error in units of its bound)."""
-    M, V = logits.shape
     inv = torch.tensor([SCALE], device=DEV)
     lg = logits.clone()
     stats = _ext.ops().ce_fwd(lg, labels, inv, write_grad)
     torch.cuda.synchronize()
+    return compare_rows(logits, labels, stats, lg, write_grad)
+
+
+def compare_rows(logits, labels, stats, lg, write_grad):
+    """Rows of one ce_fwd call against fp64: ``logits`` [M, V] as they went in, ``stats`` [4, M] and ``lg`` [M, V] (the
+    same memory after the call) as they came out: all of a call, or the same rows taken from a larger one. Returns
+    the measured maxima (loss and lse absolute error; with the gradient, its worst error in units of its bound)."""
+    M, V = logits.shape
     assert stats.shape == (4, M) and stats.dtype == torch.float32
     x = logits.double()
     valid = labels != -100
@@ -51,8 +58,10 @@ def _check(logits, labels, write_grad):
     correct = (_first_max(x) == labels) & valid
     got = stats.double()
     assert torch.isfinite(stats).all(), stats
+    figs = {}
     for name, g, w in (("loss", got[0], loss), ("lse", got[1], lse)):
         err = (g - w).abs()
+        figs[name] = err.max().item()
         print(f"ce V={V} M={M} grad={write_grad}: max {name} error {err.max().item():.3e}")
         bad = err > 1e-4 + 1e-5 * w.abs()
         assert not bool(bad.any()), (name, bad.nonzero().flatten().tolist(), g[bad].tolist(), w[bad].tolist())
@@ -61,7 +70,7 @@ def _check(logits, labels, write_grad):
     assert torch.equal(stats[3].bool(), correct), (stats[3].tolist(), correct.tolist(), labels.tolist())
     if not write_grad:
         assert torch.equal(lg.view(torch.int16), logits.view(torch.int16))  # untouched, bit for bit
-        return
+        return figs
     assert not bool(torch.isnan(lg).any())
     onehot = torch.zeros_like(p)
     onehot[valid, labels[valid]] = 1.0
@@ -71,6 +80,8 @@ def _check(logits, labels, write_grad):
     print(f"ce V={V} M={M}: max gradient error {over.max().item():.3f} of its bound")
     assert bool((over <= 1).all()), ((over > 1).nonzero()[:4].tolist(), over.max().item())
     assert bool((lg[~valid] == 0).all())  # ignored rows: exactly zero
+    figs["grad"] = over.max().item()
+    return figs
 
 
 def _edge_rows(V, seed):

@@ -7,15 +7,14 @@ dropped, doubled or misplaced k element, token block, row or column anywhere fai
 seeded random integers (tests/_blockwise.py int_operand), not arithmetic patterns, which cannot see a permutation by a
 multiple of their period. Routes the launcher picks by itself (wave tails, hybrid split-K, multi-problem grids) are also
 checked to have run, through the dispatch trace."""
-import contextlib
-
 import pytest
 import torch
 
 from llm_fine_tune_distributed_amd.ops import _ext
 from llm_fine_tune_distributed_amd.ops import reference as ref
 
-from _blockwise import assert_blocks_close, int_operand, swiglu_bwd_reference
+from _blockwise import assert_blocks_close, assert_exact, exact, int_operand, swiglu_bwd_reference, traced
+from _blockwise import mismatch as _mismatch
 
 pytestmark = pytest.mark.gpu
 
@@ -25,41 +24,6 @@ DEV = "cuda"
 @pytest.fixture(scope="module", autouse=True)
 def _ext_loaded():
     assert _ext.load(), _ext.load_error()
-
-
-@contextlib.contextmanager
-def traced():
-    """Collects the dispatch trace of the launches inside the block: ``box`` maps kernel-route names to counts."""
-    ops, box = _ext.ops(), {}
-    ops.dispatch_trace(True)
-    try:
-        yield box
-    finally:
-        ops.dispatch_trace(False)
-        box.update(kv.split("=") for kv in ops.dispatch_trace_read().split(";") if kv)
-
-
-def exact(a32: torch.Tensor) -> torch.Tensor:
-    """bf16 of an exact fp32 integer result (the one rounding the kernel may make)."""
-    assert a32.dtype == torch.float32 and a32.abs().max().item() < 2 ** 24
-    return a32.to(torch.bfloat16)
-
-
-def _mismatch(out, want):
-    """Where two tensors differ, for the assertion message: count, first index, the 256 x 256 tiles touched."""
-    bad = (out != want).nonzero()
-    if bad.numel() == 0:
-        return "equal"
-    tiles = torch.unique(bad // 256, dim=0)
-    first = tuple(bad[0].tolist())
-    return (f"{bad.shape[0]} of {out.numel()} elements differ, first at {list(first)} "
-            f"(got {out[first].item()}, want {want[first].item()}), "
-            f"{tiles.shape[0]} 256x256 tiles touched, e.g. {tiles[:4].tolist()}")
-
-
-def assert_exact(out, want, what=""):
-    assert out.shape == want.shape and out.dtype == want.dtype, (what, out.shape, want.shape)
-    assert torch.equal(out, want), (what, _mismatch(out, want))
 
 
 # ------------------------------------------------------------------------------------------------ 1a: forward gemm_tn

@@ -43,6 +43,35 @@ def test_wgrad_routing_under_a_cu_budget(monkeypatch):
         "o": 314, "qkv": 214, "down": 1214, "lm_head": 1214, "gate_up": 14}
 
 
+def test_wgrad_routing_leaves_the_4_wave_ring_at_2_pow_32_bytes(monkeypatch):
+    """The 4-wave ring (c = 14) addresses the token axis in 32-bit byte offsets (csrc/gemm_4w.hip check_tr_span):
+    _wgrad_cfg hands it no operand with T x pitch x 2 >= 2^32. At T = 8192 nothing changes: the values below are what
+    the routing returned before the bound existed (SmolLM3-3B, its LoRA r = 16 adapters, Llama-3-8B)."""
+    import torch
+    import llm_fine_tune_distributed_amd.ops.fused as F
+    monkeypatch.setattr(F, "_WGRAD_MODE", "auto")
+    monkeypatch.setattr(F, "_CU_BUDGET", 256)
+    at_8192 = {(2048, 2048): 414, (3072, 2048): 214, (2048, 11008): 1214, (128256, 2048): 1214, (22016, 2048): 14,
+               (16, 2048): 0, (16, 11008): 0, (2048, 16): 0, (3072, 16): 0, (22016, 16): 0,
+               (4096, 4096): 14, (6144, 4096): 1214, (4096, 14336): 14, (28672, 4096): 14, (128256, 4096): 1214}
+    assert {s: F._wgrad_cfg(8192, *s) for s in at_8192} == at_8192
+    assert F._wgrad_cfg(16640, 128256, 2048) == 1214      # 16640 x 128256 x 2 = 4.268e9 < 2^32
+    assert F._wgrad_cfg(16640, 128256, 256) == 1214
+    # past the bound: the pointer-advancing 8-wave rings
+    assert F._wgrad_cfg(16768, 128256, 2048) == 10 and F._wgrad_cfg(17408, 128256, 4096) == 10
+    assert F._wgrad_cfg(17408, 128256, 512) == 10 and F._wgrad_cfg(17408, 128256, 256) == 9
+    # either operand's pitch counts: a narrow x read in place from a [T, 128256] buffer
+    assert F._wgrad_cfg(17408, 256, 256, ld_x=128256) % 100 != 14 and F._wgrad_cfg(17408, 256, 256) % 100 == 14
+    assert F._wgrad_cfg(16640, 256, 256, ld_x=128256) % 100 == 14
+    assert F._g4_tr_fits(16743, 128256) and not F._g4_tr_fits(16744, 128256)
+    # the input gradient: cfg 14 only while a 256-row tile of dy and the K rows of w stay below 2^32 bytes
+    dy = torch.empty(17408, 128256, device="meta")
+    assert F._dgrad_cfg(dy, N=256, ld_w=256) == 14
+    assert F._dgrad_cfg(dy, N=256, ld_w=16768) != 14      # 128256 rows of pitch 16768: 4.30e9 bytes
+    wide = torch.empty(256, 2 ** 23, device="meta")[:, :2048]
+    assert F._dgrad_cfg(wide, N=2048) != 14               # a 256-row tile at pitch 2^23 spans 2^32 bytes
+
+
 def test_weight_gradient_pair_planning():
     """Pair planning (ops.fused): pairs smaller than one round split every tile s ways (o_proj + qkv: 64 + 96 tiles ->
     3 ways, 2 rounds of third-tiles); larger pairs run whole rounds + the split leftover (0); CPU tensors never pair."""

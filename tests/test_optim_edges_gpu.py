@@ -76,16 +76,26 @@ ADAMW_CASES = [(variant, seed, moments, n, off)
 
 @pytest.mark.parametrize("variant,sr_seed,moments,n,sr_offset", ADAMW_CASES)
 def test_adamw_variants_match_reference(variant, sr_seed, moments, n, sr_offset):
+    before = _state(n, moments, variant == "master", 11 + n % 1000)
+    after = [None if t is None else t.clone() for t in before]
+    _kernel_step(*after, sr_seed, sr_offset)
+    figs = check_against_reference(before, after, moments, sr_seed, sr_offset)
+    print(f"\n[optim] adamw {variant} moments={moments} n={n} off={sr_offset}: {figs}")
+
+
+def check_against_reference(before, after, moments, sr_seed, sr_offset):
+    """``before`` = (p, grad, master or None, m, v) as they went into one kernel step (left unchanged), ``after`` the
+    same tensors as the kernel left them (all of a call, or a range of a larger one with ``sr_offset`` advanced by its
+    start): against ops/reference.py adamw_ under the tolerances of the module docstring. Returns the figures."""
     h = HYPER
-    p, grad, ms, m, v = _state(n, moments, variant == "master", 11 + n % 1000)
-    p2, m2, v2 = p.clone(), m.clone(), v.clone()
-    ms2 = ms.clone() if ms is not None else None
-    w0 = ms.clone() if ms is not None else p.float()
-    alt_w, alt_m, alt_v = rw.adamw_kernel_order(w0, grad.float() * COEF, m.float(), v.float(), h["lr"], h["b1"],
+    p2, grad, ms2, m2, v2 = [None if t is None else t.clone() for t in before]
+    p, _, ms, m, v = after
+    w0 = ms2.clone() if ms2 is not None else p2.float()
+    alt_w, alt_m, alt_v = rw.adamw_kernel_order(w0, grad.float() * COEF, m2.float(), v2.float(), h["lr"], h["b1"],
                                                 h["b2"], h["eps"], h["wd"], 1 - h["b1"] ** STEP, 1 - h["b2"] ** STEP)
-    _kernel_step(p, grad, ms, m, v, sr_seed, sr_offset)
     ref.adamw_(p2, grad.float() * COEF, m2, v2, ms2, h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], STEP,
                sr_seed=sr_seed, sr_offset=sr_offset)
+    assert torch.equal(after[1], grad)  # the gradient is only read
     figs = []
     for name, a, b, alt in (("m", m, m2, alt_m), ("v", v, v2, alt_v)):
         assert a.dtype == b.dtype == moments
@@ -98,7 +108,7 @@ def test_adamw_variants_match_reference(variant, sr_seed, moments, n, sr_offset)
         assert torch.equal(p, ms.to(BF16))  # the working copy is the master rounded once
     else:
         figs.append(("p", _check_bf16(p, p2, "p")))
-    print(f"\n[optim] adamw {variant} moments={moments} n={n} off={sr_offset}: {figs}")
+    return figs
 
 
 @pytest.mark.parametrize("moments", [torch.float32, BF16])
