@@ -89,6 +89,11 @@ TORCH_LIBRARY(sftamd, m) {
   // loss
   // label_smoothing e in [0, 1) (HF LabelSmoother) or loss_mode 1 = dft (TRL dft_loss); stats row 0 is the objective
   m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0) -> Tensor");
+  // knowledge distillation (csrc/distill.hip): TRL's generalized JSD of the student's against the teacher's logits
+  // at temperature tau, beta 0 = KL(teacher || student), 1 = KL(student || teacher); stats [5, M] = (loss, student
+  // lse, teacher lse, student argmax == label, student argmax == teacher argmax); write_grad leaves the gradient
+  // over student_logits
+  m.def("kd_fwd(Tensor(a!) student_logits, Tensor teacher_logits, Tensor labels, Tensor inv_count, bool write_grad, float beta, float temperature) -> Tensor");
   // sequence-level objectives (csrc/preference.hip): logps[s] = -sum nll[cu[s] : cu[s + 1]]; rows of sequence s times
   // coef[s] * gscale (rows at or past cu[n_seqs]: 0); DPO per-pair stats [5, P] = (loss, coef, reward_c, reward_r, delta)
   m.def("seq_logp_sum(Tensor nll, Tensor cu_seqlens, int n_seqs) -> Tensor");

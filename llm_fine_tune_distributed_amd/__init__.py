@@ -1,7 +1,8 @@
 """MI355X-native distributed SFT framework (capabilities of thesteve0/llm-fine-tune-distributed).
 
 Public API mirrors the reference's TRL surface: ``SFTConfig`` + ``SFTTrainer(...).train()``, and for preference
-training ``DPOConfig`` + ``DPOTrainer(...).train()``.
+training ``DPOConfig`` + ``DPOTrainer(...).train()``, for knowledge distillation ``GKDConfig`` +
+``GKDTrainer(..., teacher_model=...).train()``.
 """
 __version__ = "0.1.0"
 
@@ -19,6 +20,12 @@ def __getattr__(name):
     if name in ("DPOTrainer",):
         from .train.dpo import DPOTrainer
         return DPOTrainer
+    if name in ("GKDConfig",):
+        from .train.config import GKDConfig
+        return GKDConfig
+    if name in ("GKDTrainer",):
+        from .train.gkd import GKDTrainer
+        return GKDTrainer
     if name in ("SFTTrainer", "TrainOutput"):
         from .train import trainer
         return getattr(trainer, name)

@@ -23,16 +23,19 @@ def main(argv=None):
     from ..data.synthetic import generate_qa, synthetic_preferences
     from ..data.tokenizer import load_tokenizer
     from ..parallel.process_group import cleanup_distributed, setup_distributed
-    from ..train import (AimCallback, DPOConfig, DPOTrainer, PerplexityCallback, SFTConfig, SFTTrainer,
-                         TrainingHistoryCallback, config_from_env)
+    from ..train import (AimCallback, DPOConfig, DPOTrainer, GKDConfig, GKDTrainer, PerplexityCallback, SFTConfig,
+                         SFTTrainer, TrainingHistoryCallback, config_from_env)
     from ..train.config import apply_overrides
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default=os.getenv("MODEL_NAME", "HuggingFaceTB/SmolLM3-3B"),
                     help="preset name or local HF directory (config.json + safetensors)")
-    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo"],
+    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo", "gkd"],
                     help="sft: supervised fine-tuning; dpo: preference training on {prompt, chosen, rejected} rows "
-                         "(a preference JSONL / parquet through --dataset; --set beta=...)")
+                         "(a preference JSONL / parquet through --dataset; --set beta=...); gkd: knowledge "
+                         "distillation of --model from --teacher on the SFT data (--set beta=... temperature=...)")
+    ap.add_argument("--teacher", default=os.getenv("TEACHER_MODEL_NAME"),
+                    help="--trainer gkd: the teacher, a preset name or local HF directory with the student's vocabulary")
     ap.add_argument("--dataset", default=os.getenv("DATASET_PATH", "data/qa_dataset.parquet"),
                     help="parquet/jsonl Q&A file; 'synthetic' (or a missing file) generates the synthetic set")
     ap.add_argument("--freeze-policy", default=os.getenv("FREEZE_POLICY", "last_n_layers"),
@@ -79,7 +82,7 @@ def main(argv=None):
     train_rows, val_rows = train_test_split(rows, test_size=0.1, seed=42)
     if st.is_main:
         print(f"Total dataset size: {len(rows):,} | train {len(train_rows):,} | val {len(val_rows):,}")
-    if a.trainer == "sft":
+    if a.trainer != "dpo":
         train_rows = [format_prompt(r) for r in train_rows]
         val_rows = [format_prompt(r) for r in val_rows]
     tok_dir = a.model if os.path.isdir(a.model) else None
@@ -93,7 +96,14 @@ def main(argv=None):
         # full mesh the cap grows with N (parallel/ddp.py plan_bucket_mb). DDP_BUCKET_CAP_MB pins it.
         cap = float(os.environ["DDP_BUCKET_CAP_MB"]) if os.environ.get("DDP_BUCKET_CAP_MB") else None
         dist_args = dict(ddp_find_unused_parameters=False, ddp_bucket_cap_mb=cap, local_rank=st.local_rank)
-    config_cls, trainer_cls = (DPOConfig, DPOTrainer) if a.trainer == "dpo" else (SFTConfig, SFTTrainer)
+    config_cls, trainer_cls = {"sft": (SFTConfig, SFTTrainer), "dpo": (DPOConfig, DPOTrainer),
+                               "gkd": (GKDConfig, GKDTrainer)}[a.trainer]
+    if a.trainer == "gkd":
+        if not a.teacher:
+            ap.error("--trainer gkd needs --teacher (a preset name or local HF directory)")
+        dist_args = dict(dist_args, teacher_model_name_or_path=a.teacher)
+    elif a.teacher:
+        ap.error("--teacher belongs to --trainer gkd")
     args = config_cls(
         output_dir=f"{out}/checkpoints", per_device_train_batch_size=env["batch_size"],
         per_device_eval_batch_size=env["batch_size"], gradient_accumulation_steps=a.grad_accum,

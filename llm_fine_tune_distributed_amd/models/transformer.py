@@ -363,8 +363,45 @@ class CausalLM(nn.Module):
             n_seqs = cu_seqlens.numel() - 1
         return ops.lm_head_seq_logps(h, self.lm_head_weight, labels, cu_seqlens, int(n_seqs))
 
+    def logits_rows(self, input_ids: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                    position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None) -> torch.Tensor:
+        """The logits of every token row, [M, vocab] in the model's dtype (M = B x T of a padded batch, pads included),
+        without an autograd graph through the LM head: what a distillation teacher hands to the student's
+        ``distill_loss`` (call it under ``torch.no_grad()``). The trunk is ``forward``'s."""
+        h, _, _ = self._hidden(input_ids, None, cu_seqlens, max_seqlen, position_ids, False)
+        return ops.lm_head_logits(h, self.lm_head_weight)
+
+    def distill_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, teacher_logits: torch.Tensor,
+                     cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
+                     position_ids: Optional[torch.Tensor] = None, num_items_in_batch=None, shift_labels: bool = True,
+                     beta: float = 0.5, temperature: float = 1.0, **_) -> CausalLMOutput:
+        """Knowledge distillation (TRL ``GKDTrainer.generalized_jsd_loss``): the generalized JSD between this model's
+        and a teacher's token distributions over the rows whose shifted label is not -100, summed and divided by
+        ``num_items_in_batch`` (the mean over those rows when None), exactly as ``forward`` normalises the
+        cross-entropy. ``teacher_logits`` [M, vocab] are a teacher's ``logits_rows`` of the same batch. ``stats`` is
+        [5, M] (loss, student lse, teacher lse, correct, agrees with the teacher's argmax) and ``metrics`` =
+        [correct, teacher-agreement count, valid]."""
+        dev = input_ids.device
+        h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+        valid = labels != -100
+        if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
+            num_items_in_batch = num_items_in_batch.resolve()
+        if num_items_in_batch is None:
+            cnt = valid.sum().clamp(min=1)
+        elif torch.is_tensor(num_items_in_batch):
+            cnt = num_items_in_batch
+        else:
+            cnt = torch.tensor(float(num_items_in_batch))
+        inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+        out = CausalLMOutput()
+        out.loss, out.stats = ops.lm_head_distill_loss(h, self.lm_head_weight, teacher_logits, labels, inv, beta,
+                                                       temperature)
+        out.num_tokens = valid.float().sum()
+        out.metrics = torch.stack([out.stats[3].sum(), out.stats[4].sum(), out.num_tokens])
+        return out
+
     def _hidden(self, input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels):
-        """The trunk shared by ``forward`` and ``sequence_logps``: batch metadata, embedding (NEFTune in training),
+        """The trunk shared by ``forward``, ``sequence_logps``, ``logits_rows`` and ``distill_loss``: batch metadata, embedding (NEFTune in training),
         the decoder layers and the final norm. Returns (h [M, hidden], the shifted flat labels or None, cu_seqlens)."""
         dev = input_ids.device
         rope_cs = None

@@ -1386,21 +1386,27 @@ class LMHeadCEFn(Function):
 
     @staticmethod
     def backward(ctx, dloss, _dstats):
-        h2d, dlogits = ctx.saved_tensors
-        w = ctx.weight
-        # the loss gradient (a device scalar: 1 for the trainer's loss.backward(), no host sync to find out) scales the
-        # two [T, hidden] operands below — ~26 us per step at 16 x 512, bitwise a no-op at 1 — rather than the
-        # [T, vocab] dlogits
-        g = dloss.float()
-        dh = dw = None
-        if ctx.needs_input_grad[0]:
-            dh = dgrad_mm(dlogits, w)
-            if g is not None:
-                dh = dh * g.to(dlogits.dtype)
-            dh = dh.view(ctx.h_shape)
-        if ctx.needs_input_grad[1]:
-            dw = _accumulate_weight_grad(w, dlogits, h2d, scale=g)
-        return dh, dw, None, None, None, None
+        return (*_lm_head_backward(ctx, dloss), None, None, None, None)
+
+
+def _lm_head_backward(ctx, dloss):
+    """(dh, dW) of an LM-head loss whose forward left dloss-free dlogits over the logits buffer (LMHeadCEFn,
+    LMHeadDistillFn): saved (h2d, dlogits), ctx.weight, ctx.h_shape."""
+    h2d, dlogits = ctx.saved_tensors
+    w = ctx.weight
+    # the loss gradient (a device scalar: 1 for the trainer's loss.backward(), no host sync to find out) scales the
+    # two [T, hidden] operands below — ~26 us per step at 16 x 512, bitwise a no-op at 1 — rather than the
+    # [T, vocab] dlogits
+    g = dloss.float()
+    dh = dw = None
+    if ctx.needs_input_grad[0]:
+        dh = dgrad_mm(dlogits, w)
+        if g is not None:
+            dh = dh * g.to(dlogits.dtype)
+        dh = dh.view(ctx.h_shape)
+    if ctx.needs_input_grad[1]:
+        dw = _accumulate_weight_grad(w, dlogits, h2d, scale=g)
+    return dh, dw
 
 
 def lm_head_cross_entropy(h, weight, labels, inv_count, label_smoothing: float = 0.0,
@@ -1413,6 +1419,73 @@ def lm_head_cross_entropy(h, weight, labels, inv_count, label_smoothing: float =
     if loss_type == "dft" and label_smoothing > 0:
         raise ValueError("loss_type='dft' takes no label smoothing")
     return LMHeadCEFn.apply(h, weight, labels, inv_count, float(label_smoothing), LOSS_MODES[loss_type])
+
+
+# ----------------------------------------------------------------------------- LM head + distillation
+def lm_head_logits(h: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """[M, vocab] logits of the LM head in h's dtype, no autograd graph (a teacher's side of a distillation step): the
+    HIP forward GEMM of LMHeadCEFn on the GPU."""
+    h2d = h.detach().reshape(-1, h.shape[-1])
+    w = weight.detach()
+    return fwd_gemm(h2d, w) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, w)
+
+
+def _kd_rows(logits: torch.Tensor, teacher_logits: torch.Tensor, labels: torch.Tensor, inv_count: torch.Tensor,
+             write_grad: bool, beta: float, temperature: float):
+    """Per-row generalized JSD against a teacher over the vocab (csrc/distill.hip; ref.generalized_jsd). Returns stats
+    [5, M] fp32 = (loss, student lse, teacher lse, correct, agrees with the teacher's argmax). If write_grad, logits is
+    overwritten in place by d(sum(loss) * inv_count) / dlogits; teacher_logits is only read."""
+    if _ext.use_hip(logits):
+        return _ext.ops().kd_fwd(logits, teacher_logits.contiguous(), labels, inv_count, write_grad, float(beta),
+                                 float(temperature))
+    loss, lse_s, lse_t, correct, agree = ref.generalized_jsd(logits, teacher_logits, labels, beta, temperature)
+    if write_grad:
+        logits.copy_(ref.generalized_jsd_grad(logits, teacher_logits, labels, inv_count, beta, temperature))
+    return torch.stack([loss, lse_s, lse_t, correct.to(loss.dtype), agree.to(loss.dtype)]).float()
+
+
+class LMHeadDistillFn(Function):
+    """loss = sum_t JSD_beta(h_t W^T / tau, teacher_t / tau) * inv_count, built like LMHeadCEFn: the student's logits
+    from the forward GEMM, dlogits written over them by the loss kernel, the same backward. The teacher's logits are
+    read in the forward only and not saved."""
+
+    @staticmethod
+    def forward(ctx, h, weight, teacher_logits, labels, inv_count, beta, temperature):
+        h2d = h.reshape(-1, h.shape[-1])
+        logits = fwd_gemm(h2d, weight) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, weight)
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        stats = _kd_rows(logits, teacher_logits, labels.reshape(-1), inv_count, need_grad, beta, temperature)
+        loss = (stats[0].sum() * inv_count.float()).reshape(())
+        if need_grad:
+            ctx.save_for_backward(h2d, logits)
+        ctx.weight = weight
+        ctx.h_shape = h.shape
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        return (*_lm_head_backward(ctx, dloss), None, None, None, None, None)
+
+
+def lm_head_distill_loss(h, weight, teacher_logits, labels, inv_count, beta: float = 0.5,
+                         temperature: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Knowledge distillation through the LM head (TRL ``GKDTrainer.generalized_jsd_loss``): ``teacher_logits``
+    [M, vocab] in h's dtype, ``labels`` already shifted (-100: the row costs nothing), ``beta`` in [0, 1] (0: forward
+    KL(teacher || student), 1: reverse KL), ``temperature`` > 0. Returns (loss, stats [5, M])."""
+    if not 0.0 <= float(beta) <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], got {beta}")
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    M = h.numel() // h.shape[-1]
+    if teacher_logits.dim() < 1 or teacher_logits.numel() != M * weight.shape[0] or \
+            teacher_logits.shape[-1] != weight.shape[0]:
+        raise ValueError(f"teacher_logits must be [{M}, {weight.shape[0]}] (the student's rows and vocabulary), got "
+                         f"{tuple(teacher_logits.shape)}")
+    if teacher_logits.requires_grad:
+        teacher_logits = teacher_logits.detach()
+    return LMHeadDistillFn.apply(h, weight, teacher_logits.reshape(M, -1), labels, inv_count, float(beta),
+                                 float(temperature))
 
 
 # ----------------------------------------------------------------------------- sequence log-probs + DPO

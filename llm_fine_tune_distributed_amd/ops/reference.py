@@ -202,6 +202,71 @@ def cross_entropy_grad(logits: torch.Tensor, labels: torch.Tensor, scale: torch.
     return g
 
 
+def _jsd_terms(student_logits: torch.Tensor, teacher_logits: torch.Tensor, beta: float, temperature: float):
+    """(lp, lq, lm) of the generalized JSD: the two log-softmaxes at ``temperature`` and, for 0 < beta < 1, the
+    mixture's log-probabilities logsumexp(lp + log(1 - beta), lq + log beta) (None at beta 0 or 1). fp64 for fp64
+    student logits, fp32 otherwise."""
+    dt = torch.float64 if student_logits.dtype == torch.float64 else torch.float32
+    a = student_logits.to(dt) / float(temperature)
+    b = teacher_logits.to(dt) / float(temperature)
+    lp = a - torch.logsumexp(a, -1, keepdim=True)
+    lq = b - torch.logsumexp(b, -1, keepdim=True)
+    lm = None
+    if 0.0 < beta < 1.0:
+        lm = torch.logaddexp(lp + math.log1p(-beta), lq + math.log(beta))
+    return lp, lq, lm
+
+
+def generalized_jsd(student_logits: torch.Tensor, teacher_logits: torch.Tensor, labels: torch.Tensor,
+                    beta: float = 0.5, temperature: float = 1.0):
+    """Per-token generalized Jensen-Shannon divergence of TRL's ``GKDTrainer.generalized_jsd_loss`` (twin of
+    csrc/distill.hip). ``labels`` are the rows' already shifted labels; a -100 row costs 0. With lp / lq the student's /
+    teacher's log-softmax of logits / temperature and p, q their exponentials, per row:
+    beta 0: sum q (lq - lp) = KL(teacher || student); beta 1: sum p (lp - lq) = KL(student || teacher); otherwise
+    beta sum q (lq - lm) + (1 - beta) sum p (lp - lm) with lm = logsumexp(lp + log(1 - beta), lq + log beta). No tau^2
+    factor (TRL has none). Returns (loss_per_token, student lse, teacher lse, student argmax == label, student argmax
+    == teacher argmax), the last two False on ignored rows."""
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], got {beta}")
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    lp, lq, lm = _jsd_terms(student_logits, teacher_logits, beta, temperature)
+    if beta == 0.0:
+        loss = (lq.exp() * (lq - lp)).sum(-1)
+    elif beta == 1.0:
+        loss = (lp.exp() * (lp - lq)).sum(-1)
+    else:
+        loss = beta * (lq.exp() * (lq - lm)).sum(-1) + (1.0 - beta) * (lp.exp() * (lp - lm)).sum(-1)
+    valid = labels != IGNORE_INDEX
+    loss = torch.where(valid, loss, torch.zeros_like(loss))
+    dt = lp.dtype
+    lse_s = torch.logsumexp(student_logits.to(dt) / float(temperature), -1)
+    lse_t = torch.logsumexp(teacher_logits.to(dt) / float(temperature), -1)
+    top = student_logits.argmax(-1)
+    return loss, lse_s, lse_t, (top == labels) & valid, (top == teacher_logits.argmax(-1)) & valid
+
+
+def generalized_jsd_grad(student_logits: torch.Tensor, teacher_logits: torch.Tensor, labels: torch.Tensor,
+                         scale: torch.Tensor, beta: float = 0.5, temperature: float = 1.0) -> torch.Tensor:
+    """d(sum of ``generalized_jsd``'s per-token loss * scale) / d student_logits, zero on ignored rows: with the names
+    of ``generalized_jsd``, times scale / temperature, p - q at beta 0, p ((lp - lq) - L) at beta 1 and otherwise
+    (1 - beta) p ((lp - lm) - K), K = sum p (lp - lm)."""
+    beta = float(beta)
+    lp, lq, lm = _jsd_terms(student_logits, teacher_logits, beta, temperature)
+    p = lp.exp()
+    if beta == 0.0:
+        g = p - lq.exp()
+    elif beta == 1.0:
+        d = lp - lq
+        g = p * (d - (p * d).sum(-1, keepdim=True))
+    else:
+        d = lp - lm
+        g = (1.0 - beta) * p * (d - (p * d).sum(-1, keepdim=True))
+    rs = (labels != IGNORE_INDEX).to(g.dtype) * (scale.to(g.dtype) / float(temperature))
+    return g * rs[:, None]
+
+
 def embedding_noise_u(idx: torch.Tensor, seed: int) -> torch.Tensor:
     """The NEFTune uniform of element index ``idx`` (int64): (2 (hash_u32 >> 9) + 1 - 2^23) 2^-23 in fp32 — the odd
     integers of (-2^23, 2^23) scaled by 2^-23: exact, symmetric about 0, never 0 or +-1 (twin of

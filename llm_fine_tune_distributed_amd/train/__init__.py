@@ -1,9 +1,10 @@
-from .config import DPOConfig, SFTConfig, apply_overrides, config_from_env, load_config_file
+from .config import DPOConfig, GKDConfig, SFTConfig, apply_overrides, config_from_env, load_config_file
 from .callbacks import (TrainerCallback, TrainerControl, TrainerState, TrainingHistoryCallback, PerplexityCallback,
                         AimCallback, JSONLLoggerCallback)
 from .trainer import SFTTrainer, TrainOutput, set_seed
 from .dpo import DPOTrainer
+from .gkd import GKDTrainer
 
 __all__ = ["SFTConfig", "config_from_env", "TrainerCallback", "TrainerControl", "TrainerState",
            "TrainingHistoryCallback", "PerplexityCallback", "AimCallback", "JSONLLoggerCallback", "SFTTrainer",
-           "TrainOutput", "set_seed", "DPOConfig", "DPOTrainer"]
+           "TrainOutput", "set_seed", "DPOConfig", "DPOTrainer", "GKDConfig", "GKDTrainer"]

@@ -339,6 +339,48 @@ def _tolerant_init(cls_init):
 DPOConfig.__init__ = _tolerant_init(DPOConfig.__init__)
 
 
+@dataclass
+class GKDConfig(SFTConfig):
+    """``SFTConfig`` plus TRL's ``GKDConfig`` fields for knowledge distillation from a teacher (train/gkd.py). Only
+    the off-policy objective is implemented: the student learns on the dataset's own completions."""
+    beta: float = 0.5          # generalized JSD: 0 = forward KL(teacher || student), 1 = reverse KL
+    temperature: float = 0.9   # both models' logits are divided by it
+    lmbda: float = 0.0         # share of on-policy (student-generated) batches; TRL's default is 0.5
+    seq_kd: bool = False       # TRL: train on teacher-generated sequences
+    teacher_model_name_or_path: Optional[str] = None  # preset name or local HF directory (or GKDTrainer(teacher_model=))
+
+    def __post_init__(self):
+        self.validate_objective()
+
+    def validate_objective(self) -> None:
+        a = self.neftune_noise_alpha
+        if a is not None and not float(a) >= 0:
+            raise ValueError(f"neftune_noise_alpha must be None or >= 0, got {a}")
+        if float(self.lmbda) != 0.0:
+            raise ValueError(f"GKDConfig: lmbda={self.lmbda} asks for on-policy student generations inside the "
+                             "training loop, which are not implemented; only lmbda=0 (learn on the dataset's "
+                             "completions) is. Note that TRL's default is lmbda=0.5, this project's is 0")
+        if self.seq_kd:
+            raise ValueError("GKDConfig: seq_kd=True (training on teacher-generated sequences) is not implemented: "
+                             "there is no generation inside the training loop")
+        if float(self.label_smoothing_factor) != 0.0:
+            raise ValueError("GKDConfig: label_smoothing_factor smooths a hard-label cross-entropy; the distillation "
+                             "objective has no hard-label term")
+        if self.loss_type != "nll":
+            raise ValueError(f"GKDConfig: loss_type={self.loss_type!r} selects a hard-label objective; the "
+                             "distillation objective is set by beta (leave loss_type at 'nll')")
+        if int(self.context_parallel_size or 1) > 1:
+            raise ValueError("GKDConfig: context_parallel_size > 1 is not supported (the teacher's forward is not "
+                             "sharded across a context-parallel group)")
+        if not 0.0 <= float(self.beta) <= 1.0:
+            raise ValueError(f"GKDConfig: beta must be in [0, 1], got {self.beta}")
+        if not float(self.temperature) > 0:
+            raise ValueError(f"GKDConfig: temperature must be > 0, got {self.temperature}")
+
+
+GKDConfig.__init__ = _tolerant_init(GKDConfig.__init__)
+
+
 def config_from_env(base: Optional[SFTConfig] = None, world_size: int = 1) -> Dict[str, Any]:
     """The reference's env contract (training.py:56-60,240): EPOCHS, BATCH_SIZE, LEARNING_RATE,
     DATA_DIR, OUTPUT_DIR, AIM_REPO. Returns the resolved values (LR scaled by world size like
