@@ -88,7 +88,9 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("embedding_bwd(Tensor dy, Tensor sorted_ids, Tensor perm, Tensor(a!) grad_weight) -> ()");
   // loss
   // label_smoothing e in [0, 1) (HF LabelSmoother) or loss_mode 1 = dft (TRL dft_loss); stats row 0 is the objective
-  m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0) -> Tensor");
+  // temperature tau != 1: the NLL, lse, entropy and argmax bit of softmax(x / tau); the gradient written is softmax(x /
+  // tau) - onehot, the chain rule's 1 / tau left to the caller's row weight (not with smoothing or dft)
+  m.def("ce_fwd(Tensor(a!) logits, Tensor labels, Tensor inv_count, bool write_grad, float label_smoothing=0.0, int loss_mode=0, float temperature=1.0) -> Tensor");
   // knowledge distillation (csrc/distill.hip): TRL's generalized JSD of the student's against the teacher's logits
   // at temperature tau, beta 0 = KL(teacher || student), 1 = KL(student || teacher); stats [5, M] = (loss, student
   // lse, teacher lse, student argmax == label, student argmax == teacher argmax); write_grad leaves the gradient
@@ -100,6 +102,12 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("scale_rows_by_seq(Tensor x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> Tensor");
   m.def("scale_rows_by_seq_(Tensor(a!) x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> ()");
   m.def("dpo_pair_fwd(Tensor logps, Tensor ref_logps, Tensor inv_pairs, float beta) -> Tensor");
+  // per-token policy objective (csrc/policy.hip; GRPO): rows [2, M] = (w l, w dl/dlogp) per completion row (labels >=
+  // 0), seq [6, S] = per-sequence sums (loss, completion tokens, low-clipped, high-clipped, KL, ratio); scale_rows is
+  // the per-row twin of scale_rows_by_seq: out[t, :] = x[t, :] * (coef[t] * gscale)
+  m.def("grpo_token_fwd(Tensor nll, Tensor? old_logps, Tensor? ref_logps, Tensor labels, Tensor adv, Tensor cu_seqlens, int n_seqs, Tensor inv_norm, float eps_low, float eps_high, float beta, bool per_seq_mean) -> (Tensor, Tensor)");
+  m.def("scale_rows(Tensor x, Tensor coef, Tensor gscale) -> Tensor");
+  m.def("scale_rows_(Tensor(a!) x, Tensor coef, Tensor gscale) -> ()");
   // attention (window > 0: causal sliding window, query i sees keys (i - window, i]; 0: none)
   m.def("flash_fwd(Tensor qkv, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, int window=0) -> (Tensor, Tensor)");
   m.def("flash_bwd(Tensor dout, Tensor qkv, Tensor out, Tensor lse, Tensor cu_seqlens, int max_seqlen, int n_q, int n_kv, int head_dim, float scale, bool causal, Tensor? delta=None, int window=0) -> Tensor");
@@ -109,6 +117,9 @@ TORCH_LIBRARY(sftamd, m) {
   // fused decode sampler: penalty -> temperature -> top-k -> top-p -> draw, device-resident state
   m.def("sample_token(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");
   m.def("sample_tokens(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, Tensor(g!) done, int eos_token_id, float temperature, int top_k, float top_p, float repetition_penalty, bool do_sample, int seed) -> ()");
+  // the full-vocabulary draw (Gumbel-max over softmax(penalised logits / temperature), no top-k / top-p) for B rows,
+  // with sample_tokens' state / outputs and the drawn token's log-probability in logp_log fp32 [B, cap]
+  m.def("sample_tokens_full(Tensor logits, Tensor(a!) presence, Tensor(b!) state, Tensor(c!)? tok_out, Tensor(d!)? pos_out, Tensor(e!)? len_out, Tensor(f!)? log, Tensor(g!) logp_log, Tensor(h!) done, int eos_token_id, float temperature, float repetition_penalty, int seed) -> ()");
   // weight-gradient GEMM: out[N,K] (+)= dy[T,N]^T x[T,K]
   m.def("wgrad_gemm(Tensor(a!) out, Tensor dy, Tensor x, bool accumulate, int cfg=14, Tensor(b!)? norm=None) -> ()");
   m.def("wgrad_gemm_multi(Tensor(a!)[] outs, Tensor[] dys, Tensor[] xs, int[] accs, Tensor(b!)[] norms, int split_all=0, int split_left=0) -> ()");

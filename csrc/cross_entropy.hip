@@ -7,8 +7,9 @@
 // Infinity-Cache resident: the launch caps the rows in flight, see ce_fwd) and overwrites it IN PLACE with the bf16 gradient
 // (softmax - onehot) * (1/num_items_in_batch): fp32 logits are never materialised.
 //
-// The objective is a template parameter (CE_NLL / CE_SMOOTH / CE_DFT below): label smoothing adds one fp32 sum(x)
-// accumulator to pass 1, DFT one weight broadcast through LDS; the plain instantiation keeps its loop bodies.
+// The objective is a template parameter (CE_NLL / CE_SMOOTH / CE_DFT / CE_TEMP below): label smoothing adds one fp32
+// sum(x) accumulator to pass 1, DFT one weight broadcast through LDS, the temperature one fp32 multiply per loaded
+// logit; the plain instantiation keeps its loop bodies.
 #include "common.h"
 
 #include <climits>
@@ -39,12 +40,15 @@ __device__ __forceinline__ void ce_merge(CEAcc& a, const CEAcc& b) {
 //   CE_NLL     loss = lse - x_y                          dlogit_i = (p_i - [i == y]) s
 //   CE_SMOOTH  loss = lse - (1 - e) x_y - e sum(x) / V   dlogit_i = (p_i - (1 - e) [i == y] - e / V) s   (HF LabelSmoother)
 //   CE_DFT     loss = w (lse - x_y), w = p_y constant    dlogit_i = w (p_i - [i == y]) s                 (TRL dft_loss)
-constexpr int CE_NLL = 0, CE_SMOOTH = 1, CE_DFT = 2;
+//   CE_TEMP    CE_NLL of z = x / tau (z_i = x_i * (1 / tau) in fp32, in both passes and for the label's logit): lse,
+//              entropy and the argmax bit are those of softmax(z); the buffer receives (softmax(z)_i - [i == y]) s,
+//              WITHOUT the chain rule's 1 / tau, which the caller puts onto its row weight (csrc/policy.hip)
+constexpr int CE_NLL = 0, CE_SMOOTH = 1, CE_DFT = 2, CE_TEMP = 3;
 
 template <int CE_U, int MODE>  // row loads in flight per thread, objective
 __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ inv_count, float* __restrict__ stats,
-                                                     int M, int V, int write_grad, float smooth) {
+                                                     int M, int V, int write_grad, float smooth) {  // (CE_TEMP: smooth carries 1 / tau)
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
   u16* lr = logits + (long)row * V;
@@ -58,6 +62,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   auto accum = [&](const uint4& raw, int v) {
     float x[8];
     unpack8(raw, x);
+    if constexpr (MODE == CE_TEMP) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] *= smooth;
+    }
     float mx = x[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
@@ -117,7 +125,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
     CEAcc a = red[0];
     for (int w = 1; w < 4; ++w) ce_merge(a, red[w]);
     const float lse = a.m + __logf(a.s);
-    const float xl = valid ? bf2f(lr[label]) : 0.f;
+    float xl = valid ? bf2f(lr[label]) : 0.f;
+    if constexpr (MODE == CE_TEMP) xl *= smooth;
     if constexpr (MODE == CE_SMOOTH) {
       const float sx = (red_sx[0] + red_sx[1]) + (red_sx[2] + red_sx[3]);
       stats[row] = valid ? (lse - (1.f - smooth) * xl - smooth * (sx / (float)V)) : 0.f;
@@ -143,6 +152,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   auto grad = [&](const uint4& raw, int v) {
     float x[8];
     unpack8(raw, x);
+    if constexpr (MODE == CE_TEMP) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] *= smooth;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float p = __expf(x[i] - lse);
@@ -182,7 +195,7 @@ static void ce_launch(u16* lg, const int64_t* lab, const float* inv, float* stat
 }
 
 at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor& inv_count, bool write_grad,
-                  double label_smoothing, int64_t loss_mode) {
+                  double label_smoothing, int64_t loss_mode, double temperature) {
   SFT_CHECK_BF16(logits);
   SFT_CHECK_CONTIG(logits);
   SFT_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
@@ -190,6 +203,9 @@ at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor&
   SFT_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "ce_fwd: label_smoothing must be in [0, 1)");
   SFT_CHECK(loss_mode == 0 || loss_mode == 1, "ce_fwd: loss_mode 0 (nll) or 1 (dft)");
   SFT_CHECK(loss_mode == 0 || label_smoothing == 0.0, "ce_fwd: dft takes no label smoothing");
+  SFT_CHECK(temperature > 0.0, "ce_fwd: temperature must be > 0");
+  SFT_CHECK(temperature == 1.0 || (label_smoothing == 0.0 && loss_mode == 0),
+            "ce_fwd: a temperature takes neither label smoothing nor dft");
   const int V = logits.size(-1);
   const int M = logits.numel() / V;
   SFT_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
@@ -216,7 +232,10 @@ at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor&
   auto* lb = lab.data_ptr<int64_t>();
   auto* ic = inv_count.data_ptr<float>();
   auto* st = stats.data_ptr<float>();
-  if (loss_mode == 1) ce_launch<CE_DFT>(lg, lb, ic, st, M, V, write_grad, 0.f, pad);
+  if (temperature != 1.0) {
+    SFT_TRACE("ce.temp");
+    ce_launch<CE_TEMP>(lg, lb, ic, st, M, V, write_grad, (float)(1.0 / temperature), pad);
+  } else if (loss_mode == 1) ce_launch<CE_DFT>(lg, lb, ic, st, M, V, write_grad, 0.f, pad);
   else if (label_smoothing > 0.0) ce_launch<CE_SMOOTH>(lg, lb, ic, st, M, V, write_grad, (float)label_smoothing, pad);
   else ce_launch<CE_NLL>(lg, lb, ic, st, M, V, write_grad, 0.f, pad);
   SFT_LAUNCH_CHECK();

@@ -225,6 +225,139 @@ __global__ __launch_bounds__(NT) void final_batched_kernel(const float* __restri
              presence + (long)b * words, done + b, eos);
 }
 
+// ---- the full-vocabulary draw (sample_tokens_full): Gumbel-max. Token i of row b gets the key z_i + g_i with
+// z = penalised logit / temperature and g_i = -log(-log u_i), u_i a counter-based uniform of (step, seed + b, i): the
+// argmax of the keys is a draw from softmax(z) over the whole vocabulary, with no sort and no cumulative sum. u has 23
+// random bits, u = (k + 0.5) 2^-23 (exact in fp32, never 0 or 1), so g lies in [-2.9, 16.7]: a token more than ~19.5
+// below the row's best key cannot win, i.e. probabilities below ~e^-16 are cut, far under a bf16 logit's resolution.
+// Ties (equal keys) go to the lowest index. The same pass keeps (max z, sum exp(z - max)) for the log-probability
+// z_tok - lse(z) of the drawn token.
+struct FullAcc {
+  float key, z;  // best key and its z
+  int idx;       // its index (lowest on a tie)
+  float m, s;    // running max z, sum exp(z - m)
+};
+
+__device__ __forceinline__ void full_merge(FullAcc& a, const FullAcc& b) {
+  if (b.key > a.key || (b.key == a.key && b.idx < a.idx)) {
+    a.key = b.key;
+    a.z = b.z;
+    a.idx = b.idx;
+  }
+  const float M = fmaxf(a.m, b.m);
+  const float ea = (a.m == -INFINITY) ? 0.f : __expf(a.m - M);
+  const float eb = (b.m == -INFINITY) ? 0.f : __expf(b.m - M);
+  a.s = a.s * ea + b.s * eb;
+  a.m = M;
+}
+
+// Block-wide full_merge in a fixed order (xor butterfly per wave, then waves 0..3 in order); the result is in thread 0.
+__device__ __forceinline__ void full_block_reduce(FullAcc& acc) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    FullAcc b;
+    b.key = __shfl_xor(acc.key, o, 64);
+    b.z = __shfl_xor(acc.z, o, 64);
+    b.idx = __shfl_xor(acc.idx, o, 64);
+    b.m = __shfl_xor(acc.m, o, 64);
+    b.s = __shfl_xor(acc.s, o, 64);
+    full_merge(acc, b);
+  }
+  __shared__ FullAcc red[NT / 64];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    acc = red[0];
+    for (int w = 1; w < NT / 64; ++w) full_merge(acc, red[w]);
+  }
+}
+
+// grid (tiles, B): one 2048-logit tile of one row; part [B, tiles, 4] = (key, z, max, sum), part_i [B, tiles] = index.
+template <typename T>
+__global__ __launch_bounds__(NT) void full_partial_kernel(const T* __restrict__ logits, int V,
+                                                          const unsigned* __restrict__ presence, int words,
+                                                          float inv_temp, float penalty, unsigned seed,
+                                                          const long long* __restrict__ state,
+                                                          float* __restrict__ part, int* __restrict__ part_i,
+                                                          const int* __restrict__ done) {
+  const int b = blockIdx.y;
+  if (done[b]) return;
+  const T* row = logits + (long)b * V;
+  const unsigned* pres_row = presence + (long)b * words;
+  const unsigned long long step = (unsigned long long)state[(long)b * 4];
+  const unsigned sd = seed + (unsigned)b;
+  const int i0 = blockIdx.x * TILE + threadIdx.x * IPT;
+  float raw[IPT];
+  load_run<T>(row, i0, V, raw);
+  const unsigned pres = (penalty != 1.f && i0 < V) ? (pres_row[i0 >> 5] >> (i0 & 31)) & 0xffu : 0u;
+  FullAcc acc{-INFINITY, -INFINITY, 0x7fffffff, -INFINITY, 0.f};
+#pragma unroll
+  for (int j = 0; j < IPT; ++j) {
+    const int i = i0 + j;
+    if (i < V) {
+      float x = raw[j];
+      if ((pres >> j) & 1u) x = x < 0.f ? x * penalty : x / penalty;
+      const float z = x * inv_temp;
+      const unsigned h = hash_u32((step << 32) | (unsigned long long)(unsigned)i, sd);
+      const float u = ((float)(h >> 9) + 0.5f) * (1.f / 8388608.f);
+      const float key = z - logf(0.f - logf(u));
+      FullAcc e{key, z, i, z, 1.f};
+      full_merge(acc, e);
+    }
+  }
+  full_block_reduce(acc);
+  if (threadIdx.x == 0) {
+    const long t = (long)b * gridDim.x + blockIdx.x;
+    part[t * 4 + 0] = acc.key;
+    part[t * 4 + 1] = acc.z;
+    part[t * 4 + 2] = acc.m;
+    part[t * 4 + 3] = acc.s;
+    part_i[t] = acc.idx;
+  }
+}
+
+// One block per row merges the row's tiles (thread t takes tiles t, t + 256, ... in order), then thread 0 writes what
+// final_body writes, plus the log-probability. The row's presence word has this one writer: a plain read-modify-write.
+__global__ __launch_bounds__(NT) void full_final_kernel(const float* __restrict__ part, const int* __restrict__ part_i,
+                                                        int tiles, int V, long long* __restrict__ state,
+                                                        long long* __restrict__ tok_out, long long* __restrict__ pos_out,
+                                                        int* __restrict__ len_out, long long* __restrict__ log,
+                                                        int log_cap, float* __restrict__ logp_log, int logp_cap,
+                                                        unsigned* __restrict__ presence, int words,
+                                                        int* __restrict__ done, int eos) {
+  const int b = blockIdx.x;
+  if (done[b]) return;
+  FullAcc acc{-INFINITY, -INFINITY, 0x7fffffff, -INFINITY, 0.f};
+  for (int t = threadIdx.x; t < tiles; t += NT) {
+    const long q = (long)b * tiles + t;
+    FullAcc e{part[q * 4], part[q * 4 + 1], part_i[q], part[q * 4 + 2], part[q * 4 + 3]};
+    full_merge(acc, e);
+  }
+  full_block_reduce(acc);
+  if (threadIdx.x != 0) return;
+  long long* st = state + (long)b * 4;
+  const long long step = st[0];
+  int tok = acc.idx;
+  if (tok < 0 || tok >= V) tok = 0;  // (a row of NaNs has no best key)
+  const float logp = acc.z - (acc.m + __logf(acc.s));
+  st[0] = step + 1;
+  st[1] = tok;
+  if (tok_out) tok_out[b] = tok;
+  if (log && step >= 0 && step < log_cap) log[(long)b * log_cap + step] = tok;
+  if (step >= 0 && step < logp_cap) logp_log[(long)b * logp_cap + step] = logp;
+  const bool finished = tok == eos;
+  if (finished) done[b] = 1;
+  if (pos_out && !finished) {
+    const long long p = st[2] + 1;
+    st[2] = p;
+    pos_out[b] = p;
+    st[3] = p + 1;
+    len_out[b] = (int)(p + 1);
+  }
+  unsigned* pw = presence + (long)b * words + (tok >> 5);
+  *pw = *pw | (1u << (tok & 31));
+}
+
 }  // namespace samp
 
 // logits [V] (bf16 or fp32). presence int32 bitmask [ceil(V/32)]. state int64 [4]. tok_out / pos_out int64 [1]
@@ -325,9 +458,76 @@ void sample_tokens(const at::Tensor& logits, at::Tensor presence, at::Tensor sta
   SFT_LAUNCH_CHECK();
 }
 
+// sample_tokens' rows, state and outputs with the draw taken from softmax(penalised logits / temperature) over the WHOLE
+// vocabulary (no top-k, no top-p): what a policy-gradient ratio needs. logp_log fp32 [B, cap] receives the drawn
+// token's log-probability under that distribution at the row's step. The draw depends only on (seed + b, the row's
+// step counter, the logits); no atomics, so a repeated call draws the same tokens.
+void sample_tokens_full(const at::Tensor& logits, at::Tensor presence, at::Tensor state,
+                        const c10::optional<at::Tensor>& tok_out, const c10::optional<at::Tensor>& pos_out,
+                        const c10::optional<at::Tensor>& len_out, const c10::optional<at::Tensor>& log,
+                        at::Tensor logp_log, at::Tensor done, int64_t eos_token_id, double temperature,
+                        double repetition_penalty, int64_t seed) {
+  SFT_CHECK_CUDA(logits);
+  SFT_CHECK(logits.dim() == 2 && logits.is_contiguous() &&
+                (logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16),
+            "sample_tokens_full: contiguous fp32/bf16 logits [B, V]");
+  const int64_t B = logits.size(0);
+  SFT_CHECK(B >= 1 && B <= 65535 && logits.size(1) >= 1 && logits.size(1) < (1L << 31) - samp::TILE,
+            "sample_tokens_full: batch size / vocabulary");
+  const int V = logits.size(1);
+  SFT_CHECK(presence.is_cuda() && presence.scalar_type() == at::kInt && presence.dim() == 2 && presence.size(0) == B &&
+                presence.size(1) >= (V + 31) / 32 && presence.is_contiguous(),
+            "sample_tokens_full: presence int32 bitmask [B, ceil(V/32)]");
+  SFT_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.dim() == 2 && state.size(0) == B &&
+                state.size(1) == 4 && state.is_contiguous(), "sample_tokens_full: state int64 [B, 4]");
+  SFT_CHECK(done.is_cuda() && done.scalar_type() == at::kInt && done.numel() == B && done.is_contiguous(),
+            "sample_tokens_full: done int32 [B]");
+  SFT_CHECK(temperature > 0.0, "sample_tokens_full: temperature must be > 0");
+  SFT_CHECK(repetition_penalty > 0.0, "sample_tokens_full: repetition_penalty must be > 0");
+  SFT_CHECK(!tok_out.has_value() || (tok_out->is_cuda() && tok_out->scalar_type() == at::kLong &&
+                                     tok_out->numel() == B && tok_out->is_contiguous()),
+            "sample_tokens_full: tok int64 [B]");
+  SFT_CHECK(!pos_out.has_value() ||
+                (len_out.has_value() && pos_out->is_cuda() && len_out->is_cuda() && pos_out->scalar_type() == at::kLong &&
+                 len_out->scalar_type() == at::kInt && pos_out->numel() == B && len_out->numel() == B &&
+                 pos_out->is_contiguous() && len_out->is_contiguous()),
+            "sample_tokens_full: pos int64 [B] / len int32 [B]");
+  SFT_CHECK(!log.has_value() || (log->is_cuda() && log->scalar_type() == at::kLong && log->dim() == 2 &&
+                                 log->size(0) == B && log->is_contiguous()), "sample_tokens_full: log int64 [B, cap]");
+  SFT_CHECK(logp_log.is_cuda() && logp_log.scalar_type() == at::kFloat && logp_log.dim() == 2 && logp_log.size(0) == B &&
+                logp_log.is_contiguous(), "sample_tokens_full: logp_log fp32 [B, cap]");
+  const int tiles = (V + samp::TILE - 1) / samp::TILE;
+  auto part = at::empty({B * tiles * 4}, logits.options().dtype(at::kFloat));
+  auto part_i = at::empty({B * tiles}, logits.options().dtype(at::kInt));
+  const float inv_t = (float)(1.0 / std::max(temperature, 1e-5));
+  const int words = presence.size(1);
+  const auto* pres = (const unsigned*)presence.data_ptr<int>();
+  const auto* st = (const long long*)state.data_ptr<int64_t>();
+  SFT_TRACE("samp.full");
+  if (logits.scalar_type() == at::kFloat)
+    samp::full_partial_kernel<float><<<dim3(tiles, B), samp::NT, 0, cur_stream()>>>(
+        logits.data_ptr<float>(), V, pres, words, inv_t, (float)repetition_penalty, (unsigned)seed, st,
+        part.data_ptr<float>(), part_i.data_ptr<int>(), done.data_ptr<int>());
+  else
+    samp::full_partial_kernel<u16><<<dim3(tiles, B), samp::NT, 0, cur_stream()>>>(
+        (const u16*)logits.data_ptr(), V, pres, words, inv_t, (float)repetition_penalty, (unsigned)seed, st,
+        part.data_ptr<float>(), part_i.data_ptr<int>(), done.data_ptr<int>());
+  SFT_LAUNCH_CHECK();
+  samp::full_final_kernel<<<B, samp::NT, 0, cur_stream()>>>(
+      part.data_ptr<float>(), part_i.data_ptr<int>(), tiles, V, (long long*)state.data_ptr<int64_t>(),
+      tok_out.has_value() ? (long long*)tok_out->data_ptr<int64_t>() : nullptr,
+      pos_out.has_value() ? (long long*)pos_out->data_ptr<int64_t>() : nullptr,
+      len_out.has_value() ? len_out->data_ptr<int>() : nullptr,
+      log.has_value() ? (long long*)log->data_ptr<int64_t>() : nullptr, log.has_value() ? (int)log->size(1) : 0,
+      logp_log.data_ptr<float>(), (int)logp_log.size(1), (unsigned*)presence.data_ptr<int>(), words,
+      done.data_ptr<int>(), (int)eos_token_id);
+  SFT_LAUNCH_CHECK();
+}
+
 TORCH_LIBRARY_IMPL(sftamd, CUDA, m) {
   m.impl("sample_token", &sample_token);
   m.impl("sample_tokens", &sample_tokens);
+  m.impl("sample_tokens_full", &sample_tokens_full);
 }
 
 }  // namespace sftamd

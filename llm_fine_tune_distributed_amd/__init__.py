@@ -2,7 +2,8 @@
 
 Public API mirrors the reference's TRL surface: ``SFTConfig`` + ``SFTTrainer(...).train()``, and for preference
 training ``DPOConfig`` + ``DPOTrainer(...).train()``, for knowledge distillation ``GKDConfig`` +
-``GKDTrainer(..., teacher_model=...).train()``.
+``GKDTrainer(..., teacher_model=...).train()``, for reinforcement learning from reward functions ``GRPOConfig`` +
+``GRPOTrainer(model, reward_funcs, ...).train()``.
 """
 __version__ = "0.1.0"
 
@@ -26,6 +27,12 @@ def __getattr__(name):
     if name in ("GKDTrainer",):
         from .train.gkd import GKDTrainer
         return GKDTrainer
+    if name in ("GRPOConfig",):
+        from .train.config import GRPOConfig
+        return GRPOConfig
+    if name in ("GRPOTrainer",):
+        from .train.grpo import GRPOTrainer
+        return GRPOTrainer
     if name in ("SFTTrainer", "TrainOutput"):
         from .train import trainer
         return getattr(trainer, name)

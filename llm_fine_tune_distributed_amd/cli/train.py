@@ -23,17 +23,23 @@ def main(argv=None):
     from ..data.synthetic import generate_qa, synthetic_preferences
     from ..data.tokenizer import load_tokenizer
     from ..parallel.process_group import cleanup_distributed, setup_distributed
-    from ..train import (AimCallback, DPOConfig, DPOTrainer, GKDConfig, GKDTrainer, PerplexityCallback, SFTConfig,
-                         SFTTrainer, TrainingHistoryCallback, config_from_env)
+    from ..train import (AimCallback, DPOConfig, DPOTrainer, GKDConfig, GKDTrainer, GRPOConfig, GRPOTrainer,
+                         PerplexityCallback, SFTConfig, SFTTrainer, TrainingHistoryCallback, config_from_env)
     from ..train.config import apply_overrides
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default=os.getenv("MODEL_NAME", "HuggingFaceTB/SmolLM3-3B"),
                     help="preset name or local HF directory (config.json + safetensors)")
-    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo", "gkd"],
+    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo", "gkd", "grpo"],
                     help="sft: supervised fine-tuning; dpo: preference training on {prompt, chosen, rejected} rows "
                          "(a preference JSONL / parquet through --dataset; --set beta=...); gkd: knowledge "
-                         "distillation of --model from --teacher on the SFT data (--set beta=... temperature=...)")
+                         "distillation of --model from --teacher on the SFT data (--set beta=... temperature=...); "
+                         "grpo: reinforcement learning from --reward functions on the questions of the Q&A data "
+                         "(--set num_generations=... max_completion_length=...)")
+    ap.add_argument("--reward", dest="rewards", action="append", default=[], metavar="PKG.MODULE:FUNCTION",
+                    help="--trainer grpo: a reward function f(prompts=, completions=, completion_ids=, **columns) -> "
+                         "list[float] (repeatable; built in: llm_fine_tune_distributed_amd.train.rewards:answer_match "
+                         "and :length_band)")
     ap.add_argument("--teacher", default=os.getenv("TEACHER_MODEL_NAME"),
                     help="--trainer gkd: the teacher, a preset name or local HF directory with the student's vocabulary")
     ap.add_argument("--dataset", default=os.getenv("DATASET_PATH", "data/qa_dataset.parquet"),
@@ -82,7 +88,13 @@ def main(argv=None):
     train_rows, val_rows = train_test_split(rows, test_size=0.1, seed=42)
     if st.is_main:
         print(f"Total dataset size: {len(rows):,} | train {len(train_rows):,} | val {len(val_rows):,}")
-    if a.trainer != "dpo":
+    if a.trainer == "grpo":  # the question is the prompt; the answer column travels to the reward functions
+        from ..data.prompts import WILDERNESS_EXPERT_SYSTEM_PROMPT as SYS
+        as_prompt = lambda r: {"prompt": [{"role": "system", "content": SYS},  # noqa: E731
+                                          {"role": "user", "content": r["full-question"]}], "answer": r["answer"]}
+        train_rows = [as_prompt(r) for r in train_rows]
+        val_rows = [as_prompt(r) for r in val_rows]
+    elif a.trainer != "dpo":
         train_rows = [format_prompt(r) for r in train_rows]
         val_rows = [format_prompt(r) for r in val_rows]
     tok_dir = a.model if os.path.isdir(a.model) else None
@@ -97,7 +109,17 @@ def main(argv=None):
         cap = float(os.environ["DDP_BUCKET_CAP_MB"]) if os.environ.get("DDP_BUCKET_CAP_MB") else None
         dist_args = dict(ddp_find_unused_parameters=False, ddp_bucket_cap_mb=cap, local_rank=st.local_rank)
     config_cls, trainer_cls = {"sft": (SFTConfig, SFTTrainer), "dpo": (DPOConfig, DPOTrainer),
-                               "gkd": (GKDConfig, GKDTrainer)}[a.trainer]
+                               "gkd": (GKDConfig, GKDTrainer), "grpo": (GRPOConfig, GRPOTrainer)}[a.trainer]
+    extra = {}
+    if a.trainer == "grpo":
+        from ..train.rewards import resolve
+        if not a.rewards:
+            ap.error("--trainer grpo needs at least one --reward pkg.module:function")
+        extra["reward_funcs"] = [resolve(r) for r in a.rewards]
+        # batches count completions (whole groups of num_generations); the best model is the best eval_reward
+        dist_args = dict(dist_args, metric_for_best_model="eval_reward", greater_is_better=True)
+    elif a.rewards:
+        ap.error("--reward belongs to --trainer grpo")
     if a.trainer == "gkd":
         if not a.teacher:
             ap.error("--trainer gkd needs --teacher (a preset name or local HF directory)")
@@ -110,18 +132,18 @@ def main(argv=None):
         learning_rate=env["scaled_learning_rate"], max_grad_norm=1.0, num_train_epochs=env["epochs"],
         max_steps=a.max_steps, logging_steps=2, logging_first_step=True, save_steps=500, bf16=True,
         eval_strategy="steps", eval_steps=10, save_strategy="steps", load_best_model_at_end=True,
-        metric_for_best_model="eval_loss", greater_is_better=False, save_total_limit=3, dataloader_pin_memory=True,
+        save_total_limit=3, dataloader_pin_memory=True,
         dataloader_num_workers=0, remove_unused_columns=False,
         gradient_checkpointing=not a.no_gradient_checkpointing, dataloader_drop_last=True,
         max_seq_length=a.max_length, packing=a.packing, ddp_backend="nccl" if st.device.type == "cuda" else "gloo",
         freeze_policy=a.freeze_policy, lr_scheduler_type=a.lr_scheduler, max_train_samples=a.max_train_samples,
         log_step_phases=a.log_step_phases, log_system_metrics_every=a.log_system_metrics_every,
-        **dist_args)
+        **{"metric_for_best_model": "eval_loss", "greater_is_better": False, **dist_args})
     args = apply_overrides(args, a.config, a.sets)
     if st.is_main:  # the resolved configuration of this run, next to its artifacts
         args.to_json(f"{out}/sft_config.json")
     trainer = trainer_cls(model=a.model, args=args, train_dataset=train_rows, eval_dataset=val_rows,
-                         processing_class=tokenizer, callbacks=[history, ppl, aim])
+                         processing_class=tokenizer, callbacks=[history, ppl, aim], **extra)
     if st.device.type == "cuda" and st.is_main:
         print(f"VRAM after model load: {torch.cuda.memory_allocated() / 2**30:.2f} GB allocated")
     result = trainer.train(resume_from_checkpoint=a.resume)

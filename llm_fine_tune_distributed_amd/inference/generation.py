@@ -15,6 +15,10 @@ sequence (``BatchKVCache``), and a ``BatchGraphDecoder`` whose captured step run
 the batched decode attention and the batched sampler, so the weights are read once per step for
 the whole batch. Element b of its result is what ``generate`` returns for prompt b with seed + b.
 
+``rollout_batch`` is the sampling side of reinforcement learning (train/grpo.py): the same batched decoder with
+``FullVocabSampler`` (``sample_tokens_full``: an unbiased draw from the whole softmax(logits / temperature), with the
+drawn tokens' log-probabilities) in the captured step.
+
 Structure: the layer sequence is written once (``_run_layers``), the final norm + lm_head once (``_logits``). A path
 is the ``attend(li, qkv)`` it passes in, which stores the step's K/V and attends: ``forward_cached`` prefill (slice
 store, flash attention), ``forward_cached`` decode (slice store, eager fp32 attention: the CPU step),
@@ -26,7 +30,7 @@ turns a step into a hipGraph; the two sampler classes share ``_presence`` and ``
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -385,6 +389,30 @@ class BatchDeviceSampler:
         ops_ext().sample_tokens(logits.contiguous(), self.presence, self.state, tok_out, pos_out, len_out, self.log,
                                 self.done, self.eos, t, k, p, rp, ds, seed)
 
+    def live_tensors(self):
+        """What a step advances (restored after a graph capture's warm-up runs)."""
+        return (self.state, self.presence, self.log, self.done)
+
+
+class FullVocabSampler(BatchDeviceSampler):
+    """BatchDeviceSampler drawing from softmax(penalised logits / temperature) over the whole vocabulary
+    (``sample_tokens_full``: Gumbel-max, no top-k / top-p), with the drawn tokens' log-probabilities under that
+    distribution in ``logp`` [B, cap]: the behaviour policy's side of a policy-gradient ratio."""
+
+    def __init__(self, vocab_size: int, device, histories, max_new_tokens: int, seed: Optional[int],
+                 eos_token_id: Optional[int], temperature: float, repetition_penalty: float):
+        super().__init__(vocab_size, device, histories, max_new_tokens, seed, eos_token_id, temperature, 0, 1.0,
+                         repetition_penalty, True)
+        self.logp = torch.zeros(self.log.shape, dtype=torch.float32, device=device)
+
+    def sample(self, logits: torch.Tensor, tok_out=None, pos_out=None, len_out=None) -> None:
+        t, _, _, rp, _, seed = self.params
+        ops_ext().sample_tokens_full(logits.contiguous(), self.presence, self.state, tok_out, pos_out, len_out,
+                                     self.log, self.logp, self.done, self.eos, t, rp, seed)
+
+    def live_tensors(self):
+        return super().live_tensors() + (self.logp,)
+
 
 class BatchGraphDecoder:
     """GraphDecoder for B sequences over a BatchKVCache: the step runs M = B rows through the same ops, with the
@@ -420,8 +448,7 @@ class BatchGraphDecoder:
                 body()
             return
         if self.sampled_graph is None:
-            self.sampled_graph = _capture(body, (self.tok, self.pos, self.len, sampler.state, sampler.presence,
-                                                 sampler.log, sampler.done))
+            self.sampled_graph = _capture(body, (self.tok, self.pos, self.len, *sampler.live_tensors()))
         for _ in range(n):
             self.sampled_graph.replay()
 
@@ -503,6 +530,13 @@ def _generate_batch_device(model, dec: BatchGraphDecoder, prompts, logits, max_n
     dev = model.model.embed_tokens.device
     sm = BatchDeviceSampler(model.config.vocab_size, dev, prompts, max_new_tokens, seed, eos_token_id, temperature,
                             top_k, top_p, repetition_penalty, do_sample)
+    return _decode_with_sampler(dec, sm, prompts, logits, max_new_tokens, use_graph, check_every)[0]
+
+
+def _decode_with_sampler(dec: BatchGraphDecoder, sm: BatchDeviceSampler, prompts, logits, max_new_tokens, use_graph,
+                         check_every: int = 16):
+    """The device decode loop for a given sampler. Returns (the rows' tokens, their draw counts)."""
+    dev = dec.tok.device
     sm.state[:, 2] = torch.tensor([len(p) - 1 for p in prompts], device=dev)  # first sampled token: position len(p)
     sm.sample(logits, dec.tok, dec.pos, dec.len)  # token 1 of every row from the prefill logits
     steps = 1
@@ -512,4 +546,85 @@ def _generate_batch_device(model, dec: BatchGraphDecoder, prompts, logits, max_n
         steps += n
     counts = sm.state[:, 0].tolist()  # tokens drawn per row: a finished row stops counting
     log = sm.log.tolist()
-    return [log[b][:counts[b]] for b in range(len(prompts))]
+    return [log[b][:counts[b]] for b in range(len(prompts))], counts
+
+
+# ----------------------------------------------------------------------------- on-policy rollouts
+@torch.no_grad()
+def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eos_token_id: Optional[int] = None,
+                  temperature: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
+                  seed: Optional[int] = None, use_graph: Optional[bool] = None,
+                  device_sampling: Optional[bool] = None) -> Tuple[List[List[int]], Optional[List[List[float]]]]:
+    """Sampled completions for reinforcement learning: ``(tokens, logps)``, row b drawn with ``seed + b`` and ending at
+    its EOS (included) or at ``max_new_tokens``. With ``top_k == 0`` every token is a draw from softmax(penalised
+    logits / temperature) over the WHOLE vocabulary and ``logps[b][i]`` is its log-probability under that distribution;
+    on the HIP path the batched graph decoder runs with ``sample_tokens_full`` inside the captured step, off it (or with
+    ``device_sampling=False``) the host loop draws with ``multinomial``. With ``1 <= top_k <= 64`` the existing device
+    sampler draws from the top k and ``logps`` is None (a truncated behaviour policy has no full-vocabulary ratio).
+    The model's ``training`` flag is restored on return."""
+    was_training = model.training
+    model.eval()
+    try:
+        B = len(prompts)
+        if B == 0:
+            return [], ([] if not top_k else None)
+        if max_new_tokens <= 0:
+            return [[] for _ in prompts], ([[] for _ in prompts] if not top_k else None)
+        if not float(temperature) > 0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if top_k is None or int(top_k) < 0:
+            raise ValueError(f"top_k must be >= 0 (0: the whole vocabulary), got {top_k}")
+        top_k = int(top_k)
+        dev = model.model.embed_tokens.device
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev,
+                             model.model.embed_tokens.dtype)
+        logits = prefill_batch(model, prompts, cache)
+        gpu_path = dev.type == "cuda" and model.config.head_dim == 128 and ops.use_hip(logits)
+        graph = gpu_path if use_graph is None else (use_graph and gpu_path)
+        dec = BatchGraphDecoder(model, cache)
+        if device_sampling is None:
+            device_sampling = top_k == 0 or DeviceSampler.supported(top_k, True)
+        if gpu_path and device_sampling:
+            V = model.config.vocab_size
+            if top_k == 0:
+                sm = FullVocabSampler(V, dev, prompts, max_new_tokens, seed, eos_token_id, temperature,
+                                      repetition_penalty)
+            else:
+                sm = BatchDeviceSampler(V, dev, prompts, max_new_tokens, seed, eos_token_id, temperature, top_k, 1.0,
+                                        repetition_penalty, True)
+            toks, counts = _decode_with_sampler(dec, sm, prompts, logits, max_new_tokens, graph)
+            if top_k:
+                return toks, None
+            lp = sm.logp.tolist()
+            return toks, [lp[b][:counts[b]] for b in range(B)]
+        gens = [torch.Generator(device=dev).manual_seed(seed + b) for b in range(B)]
+        hist = [torch.tensor(p, device=dev) for p in prompts]
+        out: List[List[int]] = [[] for _ in prompts]
+        lps: List[List[float]] = [[] for _ in prompts]
+        live = [True] * B
+        last = [0] * B
+        for i in range(max_new_tokens):
+            for b in range(B):
+                if not live[b]:
+                    continue
+                t = sample_next(logits[b], hist[b], temperature, top_k, None, repetition_penalty, True, gens[b])
+                if not top_k:
+                    z = logits[b].clone()
+                    if repetition_penalty != 1.0 and hist[b].numel():
+                        sc = z[hist[b]]
+                        z[hist[b]] = torch.where(sc < 0, sc * repetition_penalty, sc / repetition_penalty)
+                    lps[b].append(float(torch.log_softmax(z / max(temperature, 1e-5), -1)[t]))
+                out[b].append(t)
+                last[b] = t
+                if eos_token_id is not None and t == eos_token_id:
+                    live[b] = False
+                else:
+                    hist[b] = torch.cat([hist[b], torch.tensor([t], device=dev)])
+            if not any(live) or i + 1 == max_new_tokens:
+                break
+            logits = dec.step(last, use_graph=graph, advance=live)
+        return out, (lps if not top_k else None)
+    finally:
+        model.train(was_training)

@@ -36,6 +36,8 @@ class CausalLMOutput:
     stats: Optional[torch.Tensor] = None  # [4, M]: loss, lse, entropy, correct (per token)
     num_tokens: Optional[torch.Tensor] = None
     metrics: Optional[torch.Tensor] = None
+    rows: Optional[torch.Tensor] = None   # policy_loss: [2, M] per-row loss and coefficient
+    seq: Optional[torch.Tensor] = None    # policy_loss: [6, S] per-sequence sums
 
 
 class RMSNorm(nn.Module):
@@ -362,6 +364,53 @@ class CausalLM(nn.Module):
         if n_seqs is None:
             n_seqs = cu_seqlens.numel() - 1
         return ops.lm_head_seq_logps(h, self.lm_head_weight, labels, cu_seqlens, int(n_seqs))
+
+    def _refuse_cp(self, what: str) -> None:
+        if len(self.model.layers) and self.model.layers[0].self_attn.cp_group is not None:
+            raise NotImplementedError(f"{what} under context parallelism: a sequence's label rows are spread over "
+                                      "the group's ranks and the per-sequence sum is not reduced across them")
+
+    def policy_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, advantages: torch.Tensor,
+                    cu_seqlens: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+                    max_seqlen: Optional[int] = None, n_seqs: Optional[int] = None, shift_labels: bool = True,
+                    num_items_in_batch=None, old_logps: Optional[torch.Tensor] = None,
+                    ref_logps: Optional[torch.Tensor] = None, eps_low: float = 0.2, eps_high: float = 0.2,
+                    beta: float = 0.0, temperature: float = 1.0, per_seq_mean: bool = False) -> CausalLMOutput:
+        """The GRPO family's clipped policy objective over the completion rows (label not -100) of the first
+        ``n_seqs`` segments, each sequence weighted by its entry of ``advantages`` [n_seqs], normalised by
+        ``num_items_in_batch`` (and, with ``per_seq_mean``, by each sequence's completion length first).
+        ``old_logps`` / ``ref_logps`` are fp32 per row [M] as ``token_logps`` returns them, or None (ratio exactly 1 /
+        no KL term). ``stats`` is the cross-entropy's [4, M] at ``temperature``; ``rows`` [2, M] and ``seq`` [6, n_seqs]
+        are ``ops.lm_head_policy_loss``'s. The trunk is ``forward``'s."""
+        self._refuse_cp("policy_loss")
+        dev = input_ids.device
+        h, labels, cu_seqlens = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+        if n_seqs is None:
+            n_seqs = cu_seqlens.numel() - 1
+        if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
+            num_items_in_batch = num_items_in_batch.resolve()
+        if num_items_in_batch is None:
+            cnt = (labels != -100).sum().clamp(min=1)
+        elif torch.is_tensor(num_items_in_batch):
+            cnt = num_items_in_batch
+        else:
+            cnt = torch.tensor(float(num_items_in_batch))
+        inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+        out = CausalLMOutput()
+        out.loss, out.stats, out.rows, out.seq = ops.lm_head_policy_loss(
+            h, self.lm_head_weight, labels, advantages, cu_seqlens, int(n_seqs), inv, old_logps, ref_logps, eps_low,
+            eps_high, beta, temperature, per_seq_mean)
+        out.num_tokens = out.seq[1].sum()
+        return out
+
+    def token_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                    position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
+                    shift_labels: bool = True, temperature: float = 1.0) -> torch.Tensor:
+        """fp32 [M]: every row's log softmax(logits / temperature) at its (shifted) label, 0 where the label is -100;
+        no autograd graph through the LM head (call it under ``torch.no_grad()``). The trunk is ``forward``'s."""
+        self._refuse_cp("token_logps")
+        h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+        return ops.lm_head_token_logps(h, self.lm_head_weight, labels, temperature)
 
     def logits_rows(self, input_ids: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
                     position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None) -> torch.Tensor:

@@ -1352,10 +1352,23 @@ LOSS_MODES = {"nll": 0, "dft": 1}
 
 
 def _ce_rows(logits: torch.Tensor, labels: torch.Tensor, inv_count: torch.Tensor, write_grad: bool,
-             label_smoothing: float = 0.0, loss_mode: int = 0):
+             label_smoothing: float = 0.0, loss_mode: int = 0, temperature: float = 1.0):
     """Per-row CE over the vocab. Returns stats [4, M] fp32 = (loss, lse, entropy, correct); ``loss`` is the
     objective's per-row value (label smoothing e, or loss_mode 1 = dft: ref.cross_entropy).
-    If write_grad, logits is overwritten in place by d(sum(loss)*inv_count)/dlogits."""
+    If write_grad, logits is overwritten in place by d(sum(loss)*inv_count)/dlogits. A ``temperature`` tau != 1 gives
+    the stats of softmax(x / tau) and, with write_grad, (softmax(x / tau) - onehot) * inv_count: the chain rule's
+    1 / tau is the caller's (LMHeadPolicyFn puts it onto its row weight)."""
+    if float(temperature) != 1.0:
+        if not float(temperature) > 0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if label_smoothing != 0 or loss_mode != 0:
+            raise ValueError("a temperature takes neither label smoothing nor dft")
+        if _ext.use_hip(logits):
+            return _ext.ops().ce_fwd(logits, labels, inv_count, write_grad, 0.0, 0, float(temperature))
+        loss, lse, correct, ent = ref.cross_entropy(logits, labels, temperature=temperature)
+        if write_grad:
+            logits.copy_(ref.cross_entropy_grad(logits, labels, inv_count, temperature=temperature))
+        return torch.stack([loss, lse, ent, correct.float()])
     if _ext.use_hip(logits):
         if label_smoothing == 0 and loss_mode == 0:  # four arguments: also what an older build (SFTAMD_LIB) takes
             return _ext.ops().ce_fwd(logits, labels, inv_count, write_grad)
@@ -1591,6 +1604,108 @@ def dpo_loss(logps, ref_logps, inv_pairs, beta: float) -> Tuple[torch.Tensor, to
     if logps.dim() != 1 or logps.numel() % 2 or ref_logps.shape != logps.shape:
         raise ValueError(f"dpo_loss: logps / ref_logps must be [2 P], got {tuple(logps.shape)} / {tuple(ref_logps.shape)}")
     return DPOLossFn.apply(logps, ref_logps, inv_pairs, float(beta))
+
+
+# ----------------------------------------------------------------------------- per-token policy objective (GRPO)
+def grpo_token_stats(nll, old_logps, ref_logps, labels, adv, cu_seqlens, n_seqs: int, inv_norm, eps_low: float = 0.2,
+                     eps_high: float = 0.2, beta: float = 0.0, per_seq_mean: bool = False):
+    """(rows [2, M] = per-row (w l, w dl/dlogp), seq [6, S] = per-sequence sums of loss, completion tokens, low-clipped,
+    high-clipped, KL, ratio) of the clipped policy objective (csrc/policy.hip grpo_token_fwd; ref.grpo_token)."""
+    if not (0.0 <= float(eps_low) < 1.0 and float(eps_high) >= 0.0 and float(beta) >= 0.0):
+        raise ValueError(f"eps_low in [0, 1), eps_high >= 0 and beta >= 0 expected, got {eps_low}, {eps_high}, {beta}")
+    if _ext.use_hip(nll) and nll.dtype == torch.float32:
+        f32 = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
+        return _ext.ops().grpo_token_fwd(nll.contiguous(), f32(old_logps), f32(ref_logps), labels.contiguous(),
+                                         adv.float().contiguous(), cu_seqlens, int(n_seqs), inv_norm, float(eps_low),
+                                         float(eps_high), float(beta), bool(per_seq_mean))
+    return ref.grpo_token(nll, old_logps, ref_logps, labels, adv, cu_seqlens, int(n_seqs), inv_norm, float(eps_low),
+                          float(eps_high), float(beta), bool(per_seq_mean))
+
+
+def scale_rows(x: torch.Tensor, coef: torch.Tensor, gscale: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """Row t times coef[t] * gscale (csrc/policy.hip; the twin ref.scale_rows is bit-equal). ``inplace`` overwrites x."""
+    if _ext.use_hip(x) and x.dtype == torch.bfloat16:
+        if inplace:
+            _ext.ops().scale_rows_(x, coef, gscale)
+            return x
+        return _ext.ops().scale_rows(x.contiguous(), coef, gscale)
+    out = ref.scale_rows(x, coef, gscale)
+    return x.copy_(out) if inplace else out
+
+
+class LMHeadPolicyFn(Function):
+    """loss = sum over the completion rows of w_t l_t, l_t the clipped-ratio objective (+ beta k3 KL) of the row's
+    log-probability under softmax(h_t W^T / tau) (grpo_token_stats). The forward leaves G = softmax - onehot over the
+    logits (ce_fwd at tau) and the per-row derivative c_t = w_t dl_t / dlogp_t in rows[1]; since dlogp_t / dlogits =
+    -G_t / tau, the backward's row weight is c_t * gscale with gscale = -dloss / tau, put onto the two [T, hidden]
+    operands (dh = diag(.) (G W), dW = G^T (diag(.) h)), never onto the [T, vocab] one."""
+
+    @staticmethod
+    def forward(ctx, h, weight, labels, adv, cu_seqlens, n_seqs, inv_norm, old_logps, ref_logps, eps_low, eps_high,
+                beta, temperature, per_seq_mean):
+        h2d = h.reshape(-1, h.shape[-1])
+        logits = fwd_gemm(h2d, weight) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, weight)
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        labels = labels.reshape(-1)
+        stats = _ce_rows(logits, labels, _const(1.0, h.device), need_grad, temperature=temperature)
+        rows, seq = grpo_token_stats(stats[0], old_logps, ref_logps, labels, adv, cu_seqlens, n_seqs, inv_norm,
+                                     eps_low, eps_high, beta, per_seq_mean)
+        if need_grad:
+            ctx.save_for_backward(h2d, logits, rows)
+        ctx.weight = weight
+        ctx.h_shape = h.shape
+        ctx.tau = float(temperature)
+        ctx.mark_non_differentiable(stats, rows, seq)
+        return rows[0].sum(), stats, rows, seq
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats, _drows, _dseq):
+        h2d, G, rows = ctx.saved_tensors
+        w = ctx.weight
+        coef = rows[1].float().contiguous()
+        gscale = (dloss.float() * (-1.0 / ctx.tau)).reshape(1)
+        dh = dw = None
+        if ctx.needs_input_grad[0]:
+            dh = scale_rows(dgrad_mm(G, w), coef, gscale, inplace=True).view(ctx.h_shape)
+        if ctx.needs_input_grad[1]:
+            # (out of place: h2d is a saved activation)
+            dw = _accumulate_weight_grad(w, G, scale_rows(h2d, coef, gscale))
+        return (dh, dw) + (None,) * 12
+
+
+def lm_head_policy_loss(h, weight, labels, adv, cu_seqlens, n_seqs: int, inv_norm, old_logps=None, ref_logps=None,
+                        eps_low: float = 0.2, eps_high: float = 0.2, beta: float = 0.0, temperature: float = 1.0,
+                        per_seq_mean: bool = False):
+    """The GRPO family's per-token objective through the LM head (TRL ``GRPOTrainer._compute_loss`` at token-level
+    importance sampling). ``labels`` are already shifted, -100 off the completions; ``adv`` fp32 [n_seqs] the
+    sequences' advantages; ``inv_norm`` a fp32 scalar tensor (1 / what the loss type normalises by); ``old_logps`` /
+    ``ref_logps`` fp32 [M] or None (None: ratio exactly 1 / no KL term). Returns (loss, the cross-entropy's stats
+    [4, M] at ``temperature``, rows [2, M], seq [6, n_seqs])."""
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    if cu_seqlens.numel() < int(n_seqs) + 1:
+        raise ValueError(f"n_seqs {n_seqs} over the {cu_seqlens.numel() - 1} segments of cu_seqlens")
+    M = h.numel() // h.shape[-1]
+    for name, t in (("old_logps", old_logps), ("ref_logps", ref_logps)):
+        if t is not None and t.numel() != M:
+            raise ValueError(f"{name} must hold one value per row ({M}), got {tuple(t.shape)}")
+    det = lambda t: None if t is None else t.detach().reshape(-1)  # noqa: E731
+    return LMHeadPolicyFn.apply(h, weight, labels, adv.detach(), cu_seqlens, int(n_seqs), inv_norm, det(old_logps),
+                                det(ref_logps), float(eps_low), float(eps_high), float(beta), float(temperature),
+                                bool(per_seq_mean))
+
+
+def lm_head_token_logps(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor,
+                        temperature: float = 1.0) -> torch.Tensor:
+    """fp32 [M]: log softmax(h_t W^T / temperature)[labels_t] per row (0 where the label is -100), no autograd graph:
+    the forward GEMM and the fused cross-entropy's stats pass (write_grad off)."""
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    h2d = h.detach().reshape(-1, h.shape[-1])
+    w = weight.detach()
+    logits = fwd_gemm(h2d, w) if _ext.use_hip(h2d) else torch.nn.functional.linear(h2d, w)
+    stats = _ce_rows(logits, labels.reshape(-1), _const(1.0, h.device), False, temperature=temperature)
+    return (0.0 - stats[0]).float()
 
 
 # ----------------------------------------------------------------------------- LoRA linear

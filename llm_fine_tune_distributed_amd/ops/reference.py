@@ -155,13 +155,26 @@ def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens:
     return out.view(M, n_q * head_dim)
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, loss_mode: int = 0):
+def _at_temperature(lf: torch.Tensor, temperature: float) -> torch.Tensor:
+    """x / tau as the kernel forms it: one fp32 product with the fp32 value of 1 / tau (tau 1: x itself)."""
+    if float(temperature) == 1.0:
+        return lf
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    return lf * torch.tensor(1.0 / float(temperature), dtype=torch.float32).item()
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, loss_mode: int = 0,
+                  temperature: float = 1.0):
     """Per-token CE in fp32 (ignore_index=-100). Returns (loss_per_token, lse, argmax_correct, entropy).
 
     The per-token loss is the objective's (twin of csrc/cross_entropy.hip): ``lse - x_y`` by default,
     ``lse - (1 - e) x_y - e sum(x) / V`` with ``label_smoothing`` e (HF ``LabelSmoother``), ``p_y (lse - x_y)`` with
-    ``loss_mode`` 1 (TRL ``dft_loss``; p_y is a constant of the gradient: see ``cross_entropy_grad``)."""
-    lf = logits.float()
+    ``loss_mode`` 1 (TRL ``dft_loss``; p_y is a constant of the gradient: see ``cross_entropy_grad``). A
+    ``temperature`` tau != 1 makes every quantity that of softmax(x / tau) (plain NLL only)."""
+    if float(temperature) != 1.0 and (label_smoothing > 0 or loss_mode != 0):
+        raise ValueError("a temperature takes neither label smoothing nor dft")
+    lf = _at_temperature(logits.float(), temperature)
     lse = torch.logsumexp(lf, dim=-1)
     valid = labels != IGNORE_INDEX
     safe = labels.clamp(min=0)
@@ -181,13 +194,15 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: f
 
 
 def cross_entropy_grad(logits: torch.Tensor, labels: torch.Tensor, scale: torch.Tensor, label_smoothing: float = 0.0,
-                       loss_mode: int = 0) -> torch.Tensor:
+                       loss_mode: int = 0, temperature: float = 1.0) -> torch.Tensor:
     """d(sum of the per-token objective of ``cross_entropy`` * scale) / dlogits in fp32, zero on ignored rows:
-    (p - onehot) scale, (p - (1 - e) onehot - e / V) scale when smoothed, p_y (p - onehot) scale for dft."""
+    (p - onehot) scale, (p - (1 - e) onehot - e / V) scale when smoothed, p_y (p - onehot) scale for dft. With a
+    ``temperature`` tau, p = softmax(x / tau) and the chain rule's 1 / tau is NOT applied (the caller's row weight
+    carries it, as csrc/cross_entropy.hip CE_TEMP leaves it)."""
     valid = labels != IGNORE_INDEX
     rows = torch.arange(logits.shape[0], device=logits.device)
     safe = labels.clamp(min=0)
-    g = torch.softmax(logits.float(), -1)
+    g = torch.softmax(_at_temperature(logits.float(), temperature), -1)
     rs = valid.float() * scale.float()
     if loss_mode == 1:
         rs = rs * g[rows, safe]
@@ -436,3 +451,66 @@ def dpo_pair(logps: torch.Tensor, ref_logps: torch.Tensor, inv_pairs: torch.Tens
     sig = torch.where(z >= 0, e, torch.ones_like(e)) / (1 + e)
     coef = (-beta * sig) * inv_pairs.to(logps.dtype).reshape(())
     return torch.stack([loss, coef, beta * (pc - rc), beta * (pr - rr), delta])
+
+
+# ----------------------------------------------------------------------------- per-token policy objective (GRPO)
+def grpo_token(nll: torch.Tensor, old_logps: Optional[torch.Tensor], ref_logps: Optional[torch.Tensor],
+               labels: torch.Tensor, adv: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int, inv_norm: torch.Tensor,
+               eps_low: float, eps_high: float, beta: float, per_seq_mean: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Twin of csrc/policy.hip grpo_token_fwd, in nll's dtype (fp64 stays fp64), with its expressions in its order. A
+    completion row is a row with ``labels >= 0`` inside one of the first ``n_seqs`` segments; for it, with lp = -nll,
+    A the sequence's advantage, r = exp(lp - old) (exactly 1 without ``old_logps``), d = ref - lp:
+        l = -min(r A, clamp(r, 1 - eps_low, 1 + eps_high) A) + beta (exp(d) - d - 1)      (no KL term without ref)
+        c = dl / dlp = -A r [r A <= clamp(r) A] + beta (1 - exp(d))
+    rows [2, M] = (w l, w c), w = inv_norm, divided by the sequence's completion rows (at least 1) with
+    ``per_seq_mean``; every other row is +0. seq [6, n_seqs] = the sequences' sums of (w l, 1, [r < 1 - eps_low and
+    A < 0], [r > 1 + eps_high and A > 0], exp(d) - d - 1, r) over their completion rows."""
+    dt = nll.dtype
+    M = nll.numel()
+    rows = torch.zeros(2, M, dtype=dt, device=nll.device)
+    seq = torch.zeros(6, n_seqs, dtype=dt, device=nll.device)
+    if n_seqs == 0 or M == 0:
+        return rows, seq
+    seg = _row_segments(M, cu_seqlens.to(nll.device), n_seqs)
+    first = int(cu_seqlens[0])
+    comp = (seg < n_seqs) & (labels.to(nll.device) >= 0) & (torch.arange(M, device=nll.device) >= first)
+    sc = seg.clamp(max=n_seqs - 1)
+    cnt = torch.zeros(n_seqs, dtype=dt, device=nll.device).index_add_(0, sc[comp], comp[comp].to(dt))
+    w = inv_norm.to(dt).reshape(()).expand(n_seqs)
+    if per_seq_mean:
+        w = w / cnt.clamp(min=1.0)
+    w, A = w[sc], adv.to(dt)[sc]
+    one = torch.ones((), dtype=dt, device=nll.device)
+    lo = one - torch.tensor(float(eps_low), dtype=dt, device=nll.device)
+    hi = one + torch.tensor(float(eps_high), dtype=dt, device=nll.device)
+    lp = 0.0 - torch.where(comp, nll, torch.zeros_like(nll))
+    r = torch.exp(lp - torch.where(comp, old_logps.to(dt), torch.zeros_like(nll))) if old_logps is not None \
+        else torch.ones_like(nll)
+    r = torch.where(comp, r, torch.ones_like(r))
+    t1 = r * A
+    t2 = torch.minimum(torch.maximum(r, lo), hi) * A
+    l = 0.0 - torch.minimum(t1, t2)
+    c = torch.where(t1 <= t2, 0.0 - t1, torch.zeros_like(t1))
+    kl = torch.zeros_like(nll)
+    if ref_logps is not None:
+        d = torch.where(comp, ref_logps.to(dt), torch.zeros_like(nll)) - lp
+        em = torch.expm1(d)  # exp(d) - 1 without the cancellation at small d
+        kl = em - d
+        l = l + beta * kl
+        c = c - beta * em
+    zero = torch.zeros_like(nll)
+    rows[0] = torch.where(comp, w * l, zero)
+    rows[1] = torch.where(comp, w * c, zero)
+    cols = (rows[0], comp.to(dt), (comp & (r < lo) & (A < 0)).to(dt), (comp & (r > hi) & (A > 0)).to(dt),
+            torch.where(comp, kl, zero), torch.where(comp, r, zero))
+    for i, v in enumerate(cols):
+        seq[i].index_add_(0, sc[comp], v[comp])
+    return rows, seq
+
+
+def scale_rows(x: torch.Tensor, coef: torch.Tensor, gscale: torch.Tensor) -> torch.Tensor:
+    """out[t, :] = x[t, :] * (coef[t] * gscale). Bit-equal to csrc/policy.hip scale_rows on bf16: the two scalars are
+    multiplied first, in fp32, then one fp32 product per element and one rounding to x's dtype (fp64 stays fp64)."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    c = coef.to(ct) * gscale.to(ct).reshape(())
+    return (x.to(ct) * c[:, None]).to(x.dtype)

@@ -381,6 +381,92 @@ class GKDConfig(SFTConfig):
 GKDConfig.__init__ = _tolerant_init(GKDConfig.__init__)
 
 
+@dataclass
+class GRPOConfig(SFTConfig):
+    """``SFTConfig`` plus TRL's ``GRPOConfig`` fields for reinforcement learning from reward functions
+    (train/grpo.py). ``per_device_train_batch_size`` counts COMPLETIONS and must be a multiple of
+    ``num_generations`` (checked by the trainer, once every override has been applied): a rank's batch is
+    ``per_device_train_batch_size / num_generations`` whole prompt groups."""
+    learning_rate: float = 1e-6             # TRL GRPOConfig's default
+    loss_type: str = "dapo"                 # dapo | grpo | dr_grpo: what the summed token losses are divided by
+    num_generations: int = 8
+    max_prompt_length: Optional[int] = 512  # prompts longer than this keep their last tokens
+    max_completion_length: int = 256
+    temperature: float = 1.0
+    top_k: int = 0                          # 0: the whole vocabulary (the unbiased rollout); 1..64: the top-k sampler
+    top_p: float = 1.0
+    repetition_penalty: float = 1.0
+    beta: float = 0.0                       # weight of the k3 KL estimator against the reference; 0: no reference
+    epsilon: float = 0.2
+    epsilon_high: Optional[float] = None    # None: epsilon
+    num_iterations: int = 1                 # optimizer steps per generated batch (mu)
+    scale_rewards: str = "group"            # group | batch | none: the std the advantages are divided by
+    reward_weights: Optional[List[float]] = None
+    mask_truncated_completions: bool = False
+    importance_sampling_level: str = "token"
+    metric_for_best_model: Optional[str] = "eval_reward"
+    greater_is_better: Optional[bool] = True
+
+    def __post_init__(self):
+        self.validate_objective()
+
+    def validate_objective(self) -> None:
+        a = self.neftune_noise_alpha
+        if a is not None and not float(a) >= 0:
+            raise ValueError(f"neftune_noise_alpha must be None or >= 0, got {a}")
+        if self.loss_type == "bnpo":
+            raise ValueError("GRPOConfig: loss_type='bnpo' normalises by the LOCAL batch's completion tokens; this "
+                             "engine normalises every loss by a global count (use 'dapo')")
+        if self.loss_type in ("nll", "dft"):
+            raise ValueError(f"GRPOConfig: loss_type={self.loss_type!r} is a supervised objective; choose 'dapo', "
+                             "'grpo' or 'dr_grpo'")
+        if self.loss_type not in ("dapo", "grpo", "dr_grpo"):
+            raise ValueError(f"GRPOConfig: loss_type must be 'dapo', 'grpo' or 'dr_grpo', got {self.loss_type!r}")
+        if self.scale_rewards is True:
+            self.scale_rewards = "group"
+        elif self.scale_rewards is False:
+            self.scale_rewards = "none"
+        if self.scale_rewards not in ("group", "batch", "none"):
+            raise ValueError(f"GRPOConfig: scale_rewards must be 'group', 'batch' or 'none', got {self.scale_rewards!r}")
+        if float(self.top_p) < 1.0:
+            raise ValueError("GRPOConfig: top_p < 1 is not supported (the full-vocabulary sampler has no nucleus cut, "
+                             "and a truncated behaviour policy biases the ratio)")
+        if self.importance_sampling_level != "token":
+            raise ValueError("GRPOConfig: importance_sampling_level='sequence' (GSPO) is not implemented; only 'token'")
+        if self.packing:
+            raise ValueError("GRPOConfig: packing=True is not supported (rollout batches are padding-free already)")
+        if float(self.label_smoothing_factor) != 0.0:
+            raise ValueError("GRPOConfig: label_smoothing_factor smooths a hard-label cross-entropy; the policy "
+                             "objective has none")
+        if int(self.context_parallel_size or 1) > 1:
+            raise ValueError("GRPOConfig: context_parallel_size > 1 is not supported (per-sequence sums are not "
+                             "reduced across a context-parallel group)")
+        G = int(self.num_generations)
+        if G < 2:
+            raise ValueError(f"GRPOConfig: num_generations must be >= 2 (a group needs a spread), got {G}")
+        if int(self.max_completion_length) < 1:
+            raise ValueError(f"GRPOConfig: max_completion_length must be >= 1, got {self.max_completion_length}")
+        if self.max_prompt_length is not None and int(self.max_prompt_length) < 1:
+            raise ValueError(f"GRPOConfig: max_prompt_length must be None or >= 1, got {self.max_prompt_length}")
+        if not float(self.temperature) > 0:
+            raise ValueError(f"GRPOConfig: temperature must be > 0, got {self.temperature}")
+        if not 0 <= int(self.top_k) <= 64:
+            raise ValueError(f"GRPOConfig: top_k must be 0 (whole vocabulary) or 1..64, got {self.top_k}")
+        if not float(self.repetition_penalty) > 0:
+            raise ValueError(f"GRPOConfig: repetition_penalty must be > 0, got {self.repetition_penalty}")
+        if not float(self.beta) >= 0:
+            raise ValueError(f"GRPOConfig: beta must be >= 0, got {self.beta}")
+        if not 0.0 <= float(self.epsilon) < 1.0:
+            raise ValueError(f"GRPOConfig: epsilon must be in [0, 1), got {self.epsilon}")
+        if self.epsilon_high is not None and not float(self.epsilon_high) >= 0:
+            raise ValueError(f"GRPOConfig: epsilon_high must be None or >= 0, got {self.epsilon_high}")
+        if int(self.num_iterations) < 1:
+            raise ValueError(f"GRPOConfig: num_iterations must be >= 1, got {self.num_iterations}")
+
+
+GRPOConfig.__init__ = _tolerant_init(GRPOConfig.__init__)
+
+
 def config_from_env(base: Optional[SFTConfig] = None, world_size: int = 1) -> Dict[str, Any]:
     """The reference's env contract (training.py:56-60,240): EPOCHS, BATCH_SIZE, LEARNING_RATE,
     DATA_DIR, OUTPUT_DIR, AIM_REPO. Returns the resolved values (LR scaled by world size like
