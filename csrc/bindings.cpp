@@ -97,14 +97,14 @@ TORCH_LIBRARY(sftamd, m) {
   // over student_logits
   m.def("kd_fwd(Tensor(a!) student_logits, Tensor teacher_logits, Tensor labels, Tensor inv_count, bool write_grad, float beta, float temperature) -> Tensor");
   // sequence-level objectives (csrc/preference.hip): logps[s] = -sum nll[cu[s] : cu[s + 1]]; rows of sequence s times
-  // coef[s] * gscale (rows at or past cu[n_seqs]: 0); DPO per-pair stats [5, P] = (loss, coef, reward_c, reward_r, delta)
+  // coef[s] * gscale (rows at or past cu[n_seqs]: 0; csrc/scale_rows.hip); DPO per-pair stats [5, P] = (loss, coef, reward_c, reward_r, delta)
   m.def("seq_logp_sum(Tensor nll, Tensor cu_seqlens, int n_seqs) -> Tensor");
   m.def("scale_rows_by_seq(Tensor x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> Tensor");
   m.def("scale_rows_by_seq_(Tensor(a!) x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> ()");
   m.def("dpo_pair_fwd(Tensor logps, Tensor ref_logps, Tensor inv_pairs, float beta) -> Tensor");
   // per-token policy objective (csrc/policy.hip; GRPO): rows [2, M] = (w l, w dl/dlogp) per completion row (labels >=
   // 0), seq [6, S] = per-sequence sums (loss, completion tokens, low-clipped, high-clipped, KL, ratio); scale_rows is
-  // the per-row twin of scale_rows_by_seq: out[t, :] = x[t, :] * (coef[t] * gscale)
+  // scale_rows_by_seq's kernel without the segment search (csrc/scale_rows.hip): out[t, :] = x[t, :] * (coef[t] * gscale)
   m.def("grpo_token_fwd(Tensor nll, Tensor? old_logps, Tensor? ref_logps, Tensor labels, Tensor adv, Tensor cu_seqlens, int n_seqs, Tensor inv_norm, float eps_low, float eps_high, float beta, bool per_seq_mean) -> (Tensor, Tensor)");
   m.def("scale_rows(Tensor x, Tensor coef, Tensor gscale) -> Tensor");
   m.def("scale_rows_(Tensor(a!) x, Tensor coef, Tensor gscale) -> ()");

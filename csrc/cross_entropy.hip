@@ -10,31 +10,12 @@
 // The objective is a template parameter (CE_NLL / CE_SMOOTH / CE_DFT / CE_TEMP below): label smoothing adds one fp32
 // sum(x) accumulator to pass 1, DFT one weight broadcast through LDS, the temperature one fp32 multiply per loaded
 // logit; the plain instantiation keeps its loop bodies.
-#include "common.h"
-
-#include <climits>
-#include <cstdlib>
+//
+// The accumulator (RowAcc, its t = sum e^(x-max)*x) with its merge and shuffle, and the rows-in-flight cap, are
+// vocab_rows.h's; the per-vector accumulation, the row loops and the gradient expression are this file's.
+#include "vocab_rows.h"
 
 namespace sftamd {
-
-struct CEAcc {
-  float m, s, t;  // running max, sum exp(x-m), sum exp(x-m)*x
-  float bv;       // best value
-  int bi;         // best index (first occurrence)
-};
-
-__device__ __forceinline__ void ce_merge(CEAcc& a, const CEAcc& b) {
-  const float M = fmaxf(a.m, b.m);
-  const float ea = (a.m == -INFINITY) ? 0.f : __expf(a.m - M);
-  const float eb = (b.m == -INFINITY) ? 0.f : __expf(b.m - M);
-  a.s = a.s * ea + b.s * eb;
-  a.t = a.t * ea + b.t * eb;
-  a.m = M;
-  if (b.bv > a.bv || (b.bv == a.bv && b.bi < a.bi)) {
-    a.bv = b.bv;
-    a.bi = b.bi;
-  }
-}
 
 // Objectives, per valid row (x the bf16 logits, y the label, p = softmax(x), s = inv_count):
 //   CE_NLL     loss = lse - x_y                          dlogit_i = (p_i - [i == y]) s
@@ -57,7 +38,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   const bool valid = label >= 0 && label < V;
   const int nvec = V / 8;
 
-  CEAcc acc{-INFINITY, 0.f, 0.f, -INFINITY, INT_MAX};
+  RowAcc acc = row_acc_empty();
   float sumx = 0.f;  // CE_SMOOTH: sum of the row's logits
   auto accum = [&](const uint4& raw, int v) {
     float x[8];
@@ -69,7 +50,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
     float mx = x[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
-    CEAcc b{mx, 0.f, 0.f, -INFINITY, INT_MAX};
+    RowAcc b{mx, 0.f, 0.f, -INFINITY, INT_MAX};
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float e = __expf(x[i] - mx);
@@ -86,10 +67,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
       for (int i = 0; i < 8; ++i) sv += x[i];
       sumx += sv;
     }
-    ce_merge(acc, b);
+    row_merge(acc, b);
   };
   // U independent 16-byte loads in flight per thread before any of them is consumed: one load per iteration
-  // leaves the row stream latency-bound (~3.5 TB/s); ties in the argmax resolve by index in ce_merge, so the
+  // leaves the row stream latency-bound (~3.5 TB/s); ties in the argmax resolve by index in row_merge, so the
   // visiting order does not change the result
   int v = tid;
   for (; v + 256 * (CE_U - 1) < nvec; v += 256 * CE_U) {
@@ -100,18 +81,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
     for (int u = 0; u < CE_U; ++u) accum(r[u], v + 256 * u);
   }
   for (; v < nvec; v += 256) accum(*(const uint4*)(lr + (long)v * 8), v);
-  // wave reduce
+  // block combine: the xor butterfly per wave, then waves 0..3 in order through LDS
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    CEAcc b;
-    b.m = __shfl_xor(acc.m, o, 64);
-    b.s = __shfl_xor(acc.s, o, 64);
-    b.t = __shfl_xor(acc.t, o, 64);
-    b.bv = __shfl_xor(acc.bv, o, 64);
-    b.bi = __shfl_xor(acc.bi, o, 64);
-    ce_merge(acc, b);
-  }
-  __shared__ CEAcc red[4];
+  for (int o = 32; o > 0; o >>= 1) row_merge(acc, row_shfl_xor(acc, o));
+  __shared__ RowAcc red[4];
   __shared__ float sh_lse;
   __shared__ float red_sx[4];  // CE_SMOOTH: the waves' sum(x)
   __shared__ float sh_w;       // CE_DFT: the row's weight p_y
@@ -122,8 +95,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   }
   __syncthreads();
   if (tid == 0) {
-    CEAcc a = red[0];
-    for (int w = 1; w < 4; ++w) ce_merge(a, red[w]);
+    RowAcc a = red[0];
+    for (int w = 1; w < 4; ++w) row_merge(a, red[w]);
     const float lse = a.m + __logf(a.s);
     float xl = valid ? bf2f(lr[label]) : 0.f;
     if constexpr (MODE == CE_TEMP) xl *= smooth;
@@ -177,20 +150,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(u16* __restrict__ logits, c
   for (; v < nvec; v += 256) grad(*(const uint4*)(lr + (long)v * 8), v);
 }
 
-// One launch of the MODE instantiation; the dynamic-LDS limit is a per-kernel attribute, so each instantiation that
-// meets a pad above 64 KB raises its own, once.
-constexpr int kMaxPad = 160 * 1024 - 1024;
-
 template <int MODE>
 static void ce_launch(u16* lg, const int64_t* lab, const float* inv, float* stats, int M, int V, bool write_grad,
                       float smooth, int pad) {
-  if (pad > 64 * 1024) {
-    static bool attr = [] {
-      return hipFuncSetAttribute((const void*)ce_fwd_kernel<4, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kMaxPad) == hipSuccess;
-    }();
-    SFT_CHECK(attr, "ce_fwd: could not raise the dynamic LDS limit");
-  }
+  allow_row_pad<ce_fwd_kernel<4, MODE>>(pad, "ce_fwd");
   ce_fwd_kernel<4, MODE><<<M, 256, pad, cur_stream()>>>(lg, lab, inv, stats, M, V, write_grad ? 1 : 0, smooth);
 }
 
@@ -214,21 +177,12 @@ at::Tensor ce_fwd(at::Tensor logits, const at::Tensor& labels, const at::Tensor&
   auto stats = at::empty({4, M}, logits.options().dtype(at::kFloat));
   if (M == 0) return stats;
   auto* lg = (u16*)logits.data_ptr();
-  // Pass 2 re-reads the row from the Infinity Cache only while the rows in flight fit it: with 8 blocks per CU the
-  // SmolLM3 bench's 2048 rows x 256 KB = 512 MB of rows in flight overflow the 256 MB cache and pass 2 goes back to HBM.
-  // With the gradient written, cap the blocks per CU so the rows in flight stay near 200 MB by reserving dynamic LDS
-  // (nothing is stored in it): 3 blocks per CU at V = 128,256 — 1.037 vs 1.227 ms per call at 8192 rows
-  // (tools/bench_ce.py, profiles/r6_memory_kernels.md); the stats-only pass (eval) keeps full occupancy.
-  int pad = 0;
-  if (write_grad) {
-    const long row_bytes = (long)V * 2;
-    const long bpc = std::max(1L, std::min(8L, (200L << 20) / ((long)num_cus() * row_bytes)));
-    if (bpc < 8) pad = (int)((160L * 1024) / bpc - 1024);
-  }
-  // The pad passes 64 KB once bpc drops to 2 (V above ~136K: 79 KB at 151,936, 159 KB at 262,144), and a launch above
-  // 64 KB of dynamic LDS needs the limit raised first (cu_hog does the same for its 81 KB). Raised once to the largest
-  // pad, bpc = 1: with the kernel's static reduction scratch (under 1 KB) the block stays within the CU's 160 KB.
-  SFT_CHECK(pad <= kMaxPad, "ce_fwd: LDS pad over the CU's 160 KB");
+  // The rows-in-flight cap (vocab_rows.h): with 8 blocks per CU the SmolLM3 bench's 2048 rows x 256 KB = 512 MB of rows
+  // in flight overflow the 256 MB cache and pass 2 goes back to HBM. With the gradient written the budget is 200 MB:
+  // 3 blocks per CU at V = 128,256 — 1.037 vs 1.227 ms per call at 8192 rows (tools/bench_ce.py,
+  // profiles/r6_memory_kernels.md), 2 above ~136K (a 79 KB pad at 151,936, 159 KB at 262,144); the stats-only pass
+  // (eval) keeps full occupancy.
+  const int pad = write_grad ? rows_in_flight_pad((long)V * 2, 200) : 0;
   auto* lb = lab.data_ptr<int64_t>();
   auto* ic = inv_count.data_ptr<float>();
   auto* st = stats.data_ptr<float>();

@@ -1,7 +1,9 @@
 // Fused knowledge-distillation loss over a 128k vocabulary for gfx950: the generalized Jensen-Shannon divergence of
 // TRL's GKDTrainer between a student's and a teacher's bf16 logits (twin: ops/reference.py generalized_jsd).
 //
-// One 256-thread block per token row, built like ce_fwd (csrc/cross_entropy.hip). With a = s / tau, b = t / tau,
+// One 256-thread block per token row; the accumulator (RowAcc, its t = the KL numerator sum e^(x-m) d, d = x - the other
+// row's value) with its merge, the row sweep and the rows-in-flight cap are vocab_rows.h's, shared with ce_fwd; the block
+// combine follows the order given there, for two accumulators at once. With a = s / tau, b = t / tau,
 // lp = a - lse(a), lq = b - lse(b), p = e^lp, q = e^lq, per valid row:
 //   KD_FKL (beta 0)  L = sum q (lq - lp)                                   dL/da_i = p_i - q_i
 //   KD_RKL (beta 1)  L = sum p (lp - lq)                                   dL/da_i = p_i ((lp_i - lq_i) - L)
@@ -14,9 +16,8 @@
 // place with bf16 dL/ds_i = dL/da_i * inv_count / tau; the teacher's row is only read. Everything stays in the log
 // domain (no log of a probability), so finite logits give a finite loss and gradient while their gap fits fp32.
 // The mode is a template parameter: the mixture's extra transcendentals are not in the two KL instantiations.
-#include "common.h"
+#include "vocab_rows.h"
 
-#include <climits>
 #include <cmath>
 #include <cstdlib>
 
@@ -24,40 +25,11 @@ namespace sftamd {
 
 constexpr int KD_FKL = 0, KD_RKL = 1, KD_MIX = 2;
 
-struct KDAcc {
-  float m, s, r;  // running max, sum e^(x-m), sum e^(x-m) d (the KL numerator; d = x - the other row's value)
-  float bv;       // best value
-  int bi;         // best index (first occurrence)
-};
-
-__device__ __forceinline__ void kd_merge(KDAcc& a, const KDAcc& b) {
-  const float M = fmaxf(a.m, b.m);
-  const float ea = (a.m == -INFINITY) ? 0.f : __expf(a.m - M);
-  const float eb = (b.m == -INFINITY) ? 0.f : __expf(b.m - M);
-  a.s = a.s * ea + b.s * eb;
-  a.r = a.r * ea + b.r * eb;
-  a.m = M;
-  if (b.bv > a.bv || (b.bv == a.bv && b.bi < a.bi)) {
-    a.bv = b.bv;
-    a.bi = b.bi;
-  }
-}
-
-__device__ __forceinline__ KDAcc kd_shfl_xor(const KDAcc& a, int o) {
-  KDAcc b;
-  b.m = __shfl_xor(a.m, o, 64);
-  b.s = __shfl_xor(a.s, o, 64);
-  b.r = __shfl_xor(a.r, o, 64);
-  b.bv = __shfl_xor(a.bv, o, 64);
-  b.bi = __shfl_xor(a.bi, o, 64);
-  return b;
-}
-
 // Eight elements x of one row (columns base .. base + 7, visited in increasing order by a thread) into its online
 // accumulator: one rescale of the running sums when the maximum moves (e^(-inf) = 0 on the first vector), then the
 // eight terms against the new maximum. NUM: also the KL numerator, sign * (xa - xb).
 template <bool NUM>
-__device__ __forceinline__ void kd_accum(KDAcc& acc, const float* x, const float* xa, const float* xb, int base) {
+__device__ __forceinline__ void kd_accum(RowAcc& acc, const float* x, const float* xa, const float* xb, int base) {
   float mx = x[0];
 #pragma unroll
   for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
@@ -75,7 +47,7 @@ __device__ __forceinline__ void kd_accum(KDAcc& acc, const float* x, const float
     }
   }
   acc.s = acc.s * sc + s;
-  if constexpr (NUM) acc.r = acc.r * sc + r;
+  if constexpr (NUM) acc.t = acc.t * sc + r;
   acc.m = M;
 }
 
@@ -94,21 +66,7 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(u16* __restrict__ student, 
   const bool valid = label >= 0 && label < V;
   const int nvec = V / 8;
 
-  // the row loop of every pass: U independent 16-byte loads of each row in flight before any is consumed
-  auto sweep = [&](auto&& body) {
-    int v = tid;
-    for (; v + 256 * (KD_U - 1) < nvec; v += 256 * KD_U) {
-      uint4 rs[KD_U], rt[KD_U];
-#pragma unroll
-      for (int u = 0; u < KD_U; ++u) {
-        rs[u] = *(const uint4*)(sr + (long)(v + 256 * u) * 8);
-        rt[u] = *(const uint4*)(tr + (long)(v + 256 * u) * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < KD_U; ++u) body(rs[u], rt[u], v + 256 * u);
-    }
-    for (; v < nvec; v += 256) body(*(const uint4*)(sr + (long)v * 8), *(const uint4*)(tr + (long)v * 8), v);
-  };
+  auto sweep = [&](auto&& body) { sweep_row_pair<KD_U>(sr, tr, nvec, tid, body); };
   auto scaled = [&](const uint4& raw, float* x) {
     unpack8(raw, x);
 #pragma unroll
@@ -116,7 +74,7 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(u16* __restrict__ student, 
   };
 
   // ---- pass 1: online (max, sum, argmax) of both rows and the mode's KL numerator
-  KDAcc as{-INFINITY, 0.f, 0.f, -INFINITY, INT_MAX}, at{-INFINITY, 0.f, 0.f, -INFINITY, INT_MAX};
+  RowAcc as = row_acc_empty(), at = row_acc_empty();
   sweep([&](const uint4& rs, const uint4& rt, int v) {
     float a[8], b[8];
     scaled(rs, a);
@@ -124,12 +82,13 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(u16* __restrict__ student, 
     kd_accum<MODE == KD_RKL>(as, a, a, b, v * 8);
     kd_accum<MODE == KD_FKL>(at, b, b, a, v * 8);
   });
+  // the block combine in the order vocab_rows.h gives, for two accumulators
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    kd_merge(as, kd_shfl_xor(as, o));
-    kd_merge(at, kd_shfl_xor(at, o));
+    row_merge(as, row_shfl_xor(as, o));
+    row_merge(at, row_shfl_xor(at, o));
   }
-  __shared__ KDAcc red_s[4], red_t[4];
+  __shared__ RowAcc red_s[4], red_t[4];
   __shared__ float red_kp[4], red_kq[4];  // KD_MIX: the waves' two mixture sums
   __shared__ float sh_lse_s, sh_lse_t, sh_c;  // sh_c: the gradient's row scalar (KD_RKL: L, KD_MIX: K)
   if ((tid & 63) == 0) {
@@ -138,16 +97,16 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(u16* __restrict__ student, 
   }
   __syncthreads();
   if (tid == 0) {
-    KDAcc a = red_s[0], b = red_t[0];
+    RowAcc a = red_s[0], b = red_t[0];
     for (int w = 1; w < 4; ++w) {
-      kd_merge(a, red_s[w]);
-      kd_merge(b, red_t[w]);
+      row_merge(a, red_s[w]);
+      row_merge(b, red_t[w]);
     }
     const float lse_s = a.m + __logf(a.s);
     const float lse_t = b.m + __logf(b.s);
-    if constexpr (MODE == KD_FKL) stats[row] = valid ? (b.r / b.s + (lse_s - lse_t)) : 0.f;
+    if constexpr (MODE == KD_FKL) stats[row] = valid ? (b.t / b.s + (lse_s - lse_t)) : 0.f;
     if constexpr (MODE == KD_RKL) {
-      const float L = a.r / a.s + (lse_t - lse_s);
+      const float L = a.t / a.s + (lse_t - lse_s);
       stats[row] = valid ? L : 0.f;
       sh_c = L;
     }
@@ -226,20 +185,10 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(u16* __restrict__ student, 
   });
 }
 
-// One launch of the MODE instantiation; the dynamic-LDS limit is a per-kernel attribute, so each instantiation that
-// meets a pad above 64 KB raises its own, once (as ce_launch does).
-constexpr int kKdMaxPad = 160 * 1024 - 1024;
-
 template <int MODE>
 static void kd_launch(u16* st, const u16* te, const int64_t* lab, const float* inv, float* stats, int M, int V,
                       bool write_grad, float beta, float inv_tau, int pad) {
-  if (pad > 64 * 1024) {
-    static bool attr = [] {
-      return hipFuncSetAttribute((const void*)kd_fwd_kernel<4, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kKdMaxPad) == hipSuccess;
-    }();
-    SFT_CHECK(attr, "kd_fwd: could not raise the dynamic LDS limit");
-  }
+  allow_row_pad<kd_fwd_kernel<4, MODE>>(pad, "kd_fwd");
   const float lb = MODE == KD_MIX ? (float)std::log((double)beta) : 0.f;
   const float l1 = MODE == KD_MIX ? (float)std::log1p(-(double)beta) : 0.f;
   kd_fwd_kernel<4, MODE><<<M, 256, pad, cur_stream()>>>(st, te, lab, inv, stats, M, V, write_grad ? 1 : 0, beta, lb,
@@ -285,20 +234,12 @@ at::Tensor kd_fwd(at::Tensor student_logits, const at::Tensor& teacher_logits, c
   if (M == 0) return stats;
   SFT_CHECK(student_logits.data_ptr() != teacher_logits.data_ptr(),
             "kd_fwd: the teacher's logits must not alias the student's (the gradient is written over the student's)");
-  // Rows in flight, as in ce_fwd, with the doubled row: the gradient pass (and the mixture's pass) re-read both rows
-  // from the Infinity Cache only while the rows in flight fit it, so with the gradient written the blocks per CU are
-  // capped by reserving dynamic LDS (nothing is stored in it) until 2 x V x 2 bytes x blocks stays near the budget.
-  // ce_fwd's 200 MB leaves ONE block per CU at V = 128,256 (a row pair is 513 KB), too few waves to cover the load
+  // The rows-in-flight cap (vocab_rows.h) with the doubled row: the gradient pass (and the mixture's pass) re-read both
+  // rows. ce_fwd's 200 MB leaves ONE block per CU at V = 128,256 (a row pair is 513 KB), too few waves to cover the load
   // latency; 300 MB (two blocks, 263 MB in flight) is the fastest of 200 / 300 / 400 / 540 / uncapped at 8192 rows:
   // 1.78 vs 1.96 / 1.96 / 1.98 / 1.98 ms forward KL, 2.51 vs 3.14 / 2.51 / 2.77 / 2.77 ms mixture
   // (tools/bench_kd.py, profiles/distill.md). The stats-only call (eval) keeps full occupancy.
-  int pad = 0;
-  if (write_grad) {
-    const long row_bytes = 2L * V * 2;
-    const long bpc = std::max(1L, std::min(8L, (kd_inflight_mb() << 20) / ((long)num_cus() * row_bytes)));
-    if (bpc < 8) pad = (int)((160L * 1024) / bpc - 1024);
-  }
-  SFT_CHECK(pad <= kKdMaxPad, "kd_fwd: LDS pad over the CU's 160 KB");
+  const int pad = write_grad ? rows_in_flight_pad(2L * V * 2, kd_inflight_mb()) : 0;
   auto* sp = (u16*)student_logits.data_ptr();
   auto* tp = (const u16*)teacher_logits.data_ptr();
   auto* lb = lab.data_ptr<int64_t>();

@@ -4,13 +4,11 @@
 // G = softmax(x / tau) - onehot in the logits buffer. grpo_token_fwd turns that NLL (lp = -nll), the sampler's / an
 // earlier pass's log-probabilities and the reference's into the clipped-ratio loss with TRL's k3 KL estimator, per
 // completion row, plus its derivative c = dl / dlp. As in csrc/preference.hip a row weight commutes with both LM-head
-// backward GEMMs (dh = diag(c) (G W), dW = G^T (diag(c) h)), so c goes onto the two [T, hidden] operands (scale_rows),
+// backward GEMMs (dh = diag(c) (G W), dW = G^T (diag(c) h)), so c goes onto the two [T, hidden] operands (scale_rows, csrc/scale_rows.hip),
 // never onto the [T, vocab] one.
 //
 // No atomics: every value has one writer and a fixed summation order, so results are run-to-run identical.
 #include "common.h"
-
-#include <algorithm>
 
 namespace sftamd {
 
@@ -125,56 +123,8 @@ std::tuple<at::Tensor, at::Tensor> grpo_token_fwd(const at::Tensor& nll, const c
   return {rows, seq};
 }
 
-// out[t, :] = bf16(float(x[t, :]) * (coef[t] * gscale)): scale_rows_by_seq_kernel without the segment search.
-// blockIdx.y strides the rows (M may pass the grid's 65535). x and out may be the same buffer (the in-place form): every
-// vector is read before it is written, by the thread that writes it.
-__global__ __launch_bounds__(256) void scale_rows_kernel(const u16* x, u16* out, const float* __restrict__ coef,
-                                                         const float* __restrict__ gscale, long M, int H) {
-  const int k = (blockIdx.x * 256 + threadIdx.x) * 8;
-  if (k >= H) return;
-  const float g = gscale[0];
-  for (long t = blockIdx.y; t < M; t += gridDim.y) {
-    const float c = coef[t] * g;
-    float v[8];
-    unpack8(*(const uint4*)(x + t * H + k), v);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] *= c;
-    *(uint4*)(out + t * H + k) = pack8(v);
-  }
-}
-
-static void scale_rows_launch(const at::Tensor& x, at::Tensor& out, const at::Tensor& coef, const at::Tensor& gscale) {
-  SFT_CHECK_CUDA(x);
-  SFT_CHECK_BF16(x);
-  SFT_CHECK_CONTIG(x);
-  SFT_CHECK(x.dim() == 2 && x.size(1) % 8 == 0, "scale_rows: x [M, H], H a multiple of 8");
-  SFT_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.dim() == 1 &&
-                coef.numel() == x.size(0), "scale_rows: coef fp32 [M] on the GPU");
-  SFT_CHECK(gscale.is_cuda() && gscale.scalar_type() == at::kFloat && gscale.numel() == 1,
-            "scale_rows: gscale a fp32 GPU scalar");
-  const long M = x.size(0);
-  const int H = x.size(1);
-  if (M == 0 || H == 0) return;
-  dim3 grid((H / 8 + 255) / 256, (unsigned)std::min<long>(M, 65535));
-  SFT_TRACE("policy.scale_rows");
-  scale_rows_kernel<<<grid, 256, 0, cur_stream()>>>((const u16*)x.data_ptr(), (u16*)out.data_ptr(),
-                                                    coef.data_ptr<float>(), gscale.data_ptr<float>(), M, H);
-  SFT_LAUNCH_CHECK();
-}
-
-at::Tensor scale_rows(const at::Tensor& x, const at::Tensor& coef, const at::Tensor& gscale) {
-  SFT_CHECK_CUDA(x);
-  auto out = at::empty_like(x);
-  scale_rows_launch(x, out, coef, gscale);
-  return out;
-}
-
-void scale_rows_(at::Tensor x, const at::Tensor& coef, const at::Tensor& gscale) { scale_rows_launch(x, x, coef, gscale); }
-
 TORCH_LIBRARY_IMPL(sftamd, CUDA, m) {
   m.impl("grpo_token_fwd", &grpo_token_fwd);
-  m.impl("scale_rows", &scale_rows);
-  m.impl("scale_rows_", &scale_rows_);
 }
 
 }  // namespace sftamd

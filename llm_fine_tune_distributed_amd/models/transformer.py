@@ -331,15 +331,7 @@ class CausalLM(nn.Module):
         out = CausalLMOutput()
         if labels is not None:
             valid = labels != -100
-            if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
-                num_items_in_batch = num_items_in_batch.resolve()
-            if num_items_in_batch is None:
-                cnt = valid.sum().clamp(min=1)
-            elif torch.is_tensor(num_items_in_batch):
-                cnt = num_items_in_batch
-            else:
-                cnt = torch.tensor(float(num_items_in_batch))
-            inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+            inv = _inv_count(num_items_in_batch, valid, dev)
             out.loss, out.stats = ops.lm_head_cross_entropy(h, self.lm_head_weight, labels, inv, label_smoothing,
                                                             loss_type)
             vf = valid.float()
@@ -357,9 +349,7 @@ class CausalLM(nn.Module):
         the first ``n_seqs`` segments of ``cu_seqlens`` (default: all of them; every row of a padded [B, T] batch).
         Returns (logps fp32 [n_seqs], differentiable; the fused cross-entropy's stats [4, M]). The trunk is
         ``forward``'s. Sequence-level objectives (DPO) build on this."""
-        if len(self.model.layers) and self.model.layers[0].self_attn.cp_group is not None:
-            raise NotImplementedError("sequence_logps under context parallelism: a sequence's label rows are spread "
-                                      "over the group's ranks and the per-sequence sum is not reduced across them")
+        self._refuse_cp("sequence_logps")
         h, labels, cu_seqlens = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
         if n_seqs is None:
             n_seqs = cu_seqlens.numel() - 1
@@ -387,15 +377,7 @@ class CausalLM(nn.Module):
         h, labels, cu_seqlens = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
         if n_seqs is None:
             n_seqs = cu_seqlens.numel() - 1
-        if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
-            num_items_in_batch = num_items_in_batch.resolve()
-        if num_items_in_batch is None:
-            cnt = (labels != -100).sum().clamp(min=1)
-        elif torch.is_tensor(num_items_in_batch):
-            cnt = num_items_in_batch
-        else:
-            cnt = torch.tensor(float(num_items_in_batch))
-        inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+        inv = _inv_count(num_items_in_batch, labels != -100, dev)
         out = CausalLMOutput()
         out.loss, out.stats, out.rows, out.seq = ops.lm_head_policy_loss(
             h, self.lm_head_weight, labels, advantages, cu_seqlens, int(n_seqs), inv, old_logps, ref_logps, eps_low,
@@ -433,15 +415,7 @@ class CausalLM(nn.Module):
         dev = input_ids.device
         h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
         valid = labels != -100
-        if hasattr(num_items_in_batch, "resolve"):  # trainer's in-flight global count (PendingCount)
-            num_items_in_batch = num_items_in_batch.resolve()
-        if num_items_in_batch is None:
-            cnt = valid.sum().clamp(min=1)
-        elif torch.is_tensor(num_items_in_batch):
-            cnt = num_items_in_batch
-        else:
-            cnt = torch.tensor(float(num_items_in_batch))
-        inv = (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
+        inv = _inv_count(num_items_in_batch, valid, dev)
         out = CausalLMOutput()
         out.loss, out.stats = ops.lm_head_distill_loss(h, self.lm_head_weight, teacher_logits, labels, inv, beta,
                                                        temperature)
@@ -450,8 +424,9 @@ class CausalLM(nn.Module):
         return out
 
     def _hidden(self, input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels):
-        """The trunk shared by ``forward``, ``sequence_logps``, ``logits_rows`` and ``distill_loss``: batch metadata, embedding (NEFTune in training),
-        the decoder layers and the final norm. Returns (h [M, hidden], the shifted flat labels or None, cu_seqlens)."""
+        """The trunk shared by ``forward``, ``sequence_logps``, ``policy_loss``, ``token_logps``, ``logits_rows`` and
+        ``distill_loss``: batch metadata, embedding (NEFTune in training), the decoder layers and the final norm.
+        Returns (h [M, hidden], the shifted flat labels or None, cu_seqlens)."""
         dev = input_ids.device
         rope_cs = None
         padded = tuple(input_ids.shape) if input_ids.dim() == 2 and cu_seqlens is None else None
@@ -581,6 +556,20 @@ def _shift_packed(labels: torch.Tensor, cu: torch.Tensor) -> torch.Tensor:
     ends = ends[ends >= 0]
     out[ends] = -100
     return out
+
+
+def _inv_count(num_items_in_batch, valid: torch.Tensor, dev) -> torch.Tensor:
+    """fp32 [1] on ``dev``: 1 / num_items_in_batch (HF semantics: a number, a tensor, or the trainer's in-flight global
+    count, PendingCount), or 1 / the number of ``valid`` rows (at least 1) when it is None."""
+    if hasattr(num_items_in_batch, "resolve"):
+        num_items_in_batch = num_items_in_batch.resolve()
+    if num_items_in_batch is None:
+        cnt = valid.sum().clamp(min=1)
+    elif torch.is_tensor(num_items_in_batch):
+        cnt = num_items_in_batch
+    else:
+        cnt = torch.tensor(float(num_items_in_batch))
+    return (1.0 / cnt.to(device=dev, dtype=torch.float32)).reshape(1)
 
 
 def build_model(cfg: ModelConfig, device="cpu", dtype=torch.bfloat16, seed: int = 0) -> CausalLM:

@@ -424,7 +424,7 @@ def seq_logp_sum(nll: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int) -> to
 def scale_rows_by_seq(x: torch.Tensor, coef: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int,
                       gscale: torch.Tensor) -> torch.Tensor:
     """out[t, :] = x[t, :] * (coef[s(t)] * gscale) with s(t) the segment of row t, +0 on rows at or past ``cu[n_seqs]``.
-    Bit-equal to csrc/preference.hip scale_rows_by_seq on bf16: the two scalars are multiplied first, in fp32, then
+    Bit-equal to csrc/scale_rows.hip scale_rows_by_seq on bf16: the two scalars are multiplied first, in fp32, then
     one fp32 product per element and one rounding to x's dtype (fp64 stays fp64)."""
     ct = torch.float64 if x.dtype == torch.float64 else torch.float32
     M = x.shape[0]
@@ -509,7 +509,7 @@ def grpo_token(nll: torch.Tensor, old_logps: Optional[torch.Tensor], ref_logps: 
 
 
 def scale_rows(x: torch.Tensor, coef: torch.Tensor, gscale: torch.Tensor) -> torch.Tensor:
-    """out[t, :] = x[t, :] * (coef[t] * gscale). Bit-equal to csrc/policy.hip scale_rows on bf16: the two scalars are
+    """out[t, :] = x[t, :] * (coef[t] * gscale). Bit-equal to csrc/scale_rows.hip scale_rows on bf16: the two scalars are
     multiplied first, in fp32, then one fp32 product per element and one rounding to x's dtype (fp64 stays fp64)."""
     ct = torch.float64 if x.dtype == torch.float64 else torch.float32
     c = coef.to(ct) * gscale.to(ct).reshape(())

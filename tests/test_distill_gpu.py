@@ -16,7 +16,7 @@ import torch
 
 from llm_fine_tune_distributed_amd import ops
 from llm_fine_tune_distributed_amd.models import build_model, get_config
-from llm_fine_tune_distributed_amd.ops import _ext, fused
+from llm_fine_tune_distributed_amd.ops import _ext, lm_head
 from llm_fine_tune_distributed_amd.ops import reference as ref
 
 from _blockwise import assert_blocks_close, block_rel_err
@@ -463,8 +463,8 @@ def gkd_run(tmp_path_factory):
     t = _gkd_trainer(out, save_steps=2)
     before = {n: p.detach().clone() for n, p in t.teacher.named_parameters()}
     ce_calls = []
-    real = fused._ce_rows
-    fused._ce_rows = lambda *a, **k: (ce_calls.append(1), real(*a, **k))[1]
+    real = lm_head._ce_rows
+    lm_head._ce_rows = lambda *a, **k: (ce_calls.append(1), real(*a, **k))[1]
     _ext.ops().dispatch_trace(True)
     try:
         t.train()
@@ -472,7 +472,7 @@ def gkd_run(tmp_path_factory):
         torch.cuda.synchronize()
     finally:
         _ext.ops().dispatch_trace(False)
-        fused._ce_rows = real
+        lm_head._ce_rows = real
     trace = {k: int(v) for k, v in (it.split("=") for it in _ext.ops().dispatch_trace_read().split(";") if it)}
     return t, before, trace, len(ce_calls), ev, out
 

@@ -135,8 +135,8 @@ def test_ce_temperature_refusals():
            lambda: o.ce_fwd(logits.clone(), labels, inv, False, 0.0, 0, -1.0),
            lambda: o.ce_fwd(logits.clone(), labels, inv, False, 0.1, 0, 0.7),
            lambda: o.ce_fwd(logits.clone(), labels, inv, False, 0.0, 1, 0.7),
-           lambda: ops.fused._ce_rows(logits.clone(), labels, inv, False, temperature=0.0),
-           lambda: ops.fused._ce_rows(logits.clone(), labels, inv, False, label_smoothing=0.1, temperature=0.7))
+           lambda: ops.lm_head._ce_rows(logits.clone(), labels, inv, False, temperature=0.0),
+           lambda: ops.lm_head._ce_rows(logits.clone(), labels, inv, False, label_smoothing=0.1, temperature=0.7))
 
 
 # ------------------------------------------------------------------------------------------------ grpo_token_fwd
