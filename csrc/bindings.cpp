@@ -102,6 +102,12 @@ TORCH_LIBRARY(sftamd, m) {
   m.def("scale_rows_by_seq(Tensor x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> Tensor");
   m.def("scale_rows_by_seq_(Tensor(a!) x, Tensor coef, Tensor cu_seqlens, int n_seqs, Tensor gscale) -> ()");
   m.def("dpo_pair_fwd(Tensor logps, Tensor ref_logps, Tensor inv_pairs, float beta) -> Tensor");
+  // reward modelling (csrc/reward.hip): scores[s] = h[last row of segment s] . w in fp32 (an empty segment: +0); its
+  // backward (dh bf16 [M, H]: g_s w on those rows, +0 elsewhere; dw fp32 [H]), the half not needed returned undefined;
+  // per-pair stats [4, P] = (softplus(-z) + c (r_c + r_r)^2, d / d r_c, d / d r_r, z), z = r_c - r_r - margin
+  m.def("seq_score_fwd(Tensor h, Tensor w, Tensor cu_seqlens, int n_seqs) -> Tensor");
+  m.def("seq_score_bwd(Tensor g, Tensor h, Tensor w, Tensor cu_seqlens, int n_seqs, bool need_dh, bool need_dw) -> (Tensor, Tensor)");
+  m.def("reward_pair_fwd(Tensor scores, Tensor? margins, Tensor inv_pairs, float center_coef) -> Tensor");
   // per-token policy objective (csrc/policy.hip; GRPO): rows [2, M] = (w l, w dl/dlogp) per completion row (labels >=
   // 0), seq [6, S] = per-sequence sums (loss, completion tokens, low-clipped, high-clipped, KL, ratio); scale_rows is
   // scale_rows_by_seq's kernel without the segment search (csrc/scale_rows.hip): out[t, :] = x[t, :] * (coef[t] * gscale)

@@ -44,6 +44,15 @@ __device__ __forceinline__ void swiglu_grad(float d, float g, float u, float& dg
   dg = ((d * u) * sg) * __builtin_fmaf(g, 1.f - sg, 1.f);
 }
 
+// The pairwise logistic losses (DPO, reward modelling) of one margin z: loss = softplus(-z) as max(-z, 0) +
+// log1p(exp(-|z|)) and sig = sigmoid(-z) through exp(-|z|) only, so nothing overflows at any z.
+__device__ __forceinline__ void softplus_sigmoid_neg(float z, float& loss, float& sig) {
+#pragma clang fp contract(off)
+  const float e = expf(-fabsf(z));
+  loss = fmaxf(-z, 0.f) + log1pf(e);
+  sig = (z >= 0.f ? e : 1.f) / (1.f + e);
+}
+
 // 8 x bf16 in a uint4 <-> 8 floats
 __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
   const unsigned w[4] = {v.x, v.y, v.z, v.w};

@@ -45,8 +45,8 @@ at::Tensor seq_logp_sum(const at::Tensor& nll, const at::Tensor& cu_seqlens, int
 }
 
 // Pair p = sequences (2p chosen, 2p + 1 rejected). stats [5, P]: loss, coef (d(inv_pairs sum loss) / d logp_chosen; the
-// rejected sequence's is its negative), reward_chosen, reward_rejected, delta. softplus(-z) as max(-z, 0) +
-// log1p(exp(-|z|)) and the sigmoid through exp(-|z|) only: no overflow at any z.
+// rejected sequence's is its negative), reward_chosen, reward_rejected, delta. softplus(-z) and the sigmoid are
+// common.h's softplus_sigmoid_neg (shared with csrc/reward.hip): no overflow at any z.
 __global__ __launch_bounds__(256) void dpo_pair_fwd_kernel(const float* __restrict__ lp, const float* __restrict__ rlp,
                                                            const float* __restrict__ inv_pairs,
                                                            float* __restrict__ stats, int P, float beta) {
@@ -56,9 +56,8 @@ __global__ __launch_bounds__(256) void dpo_pair_fwd_kernel(const float* __restri
   const float pc = lp[2 * p], pr = lp[2 * p + 1], rc = rlp[2 * p], rr = rlp[2 * p + 1];
   const float delta = (pc - pr) - (rc - rr);
   const float z = beta * delta;
-  const float e = expf(-fabsf(z));
-  const float loss = fmaxf(-z, 0.f) + log1pf(e);
-  const float sig = (z >= 0.f ? e : 1.f) / (1.f + e);  // sigmoid(-z)
+  float loss, sig;  // softplus(-z), sigmoid(-z)
+  softplus_sigmoid_neg(z, loss, sig);
   stats[p] = loss;
   stats[P + p] = (-beta * sig) * inv_pairs[0];
   stats[2 * P + p] = beta * (pc - rc);

@@ -3,7 +3,8 @@
 Public API mirrors the reference's TRL surface: ``SFTConfig`` + ``SFTTrainer(...).train()``, and for preference
 training ``DPOConfig`` + ``DPOTrainer(...).train()``, for knowledge distillation ``GKDConfig`` +
 ``GKDTrainer(..., teacher_model=...).train()``, for reinforcement learning from reward functions ``GRPOConfig`` +
-``GRPOTrainer(model, reward_funcs, ...).train()``.
+``GRPOTrainer(model, reward_funcs, ...).train()``, for reward modelling on preference pairs ``RewardConfig`` +
+``RewardTrainer(...).train()`` (its models are also ``GRPOTrainer`` reward functions).
 """
 __version__ = "0.1.0"
 
@@ -33,6 +34,12 @@ def __getattr__(name):
     if name in ("GRPOTrainer",):
         from .train.grpo import GRPOTrainer
         return GRPOTrainer
+    if name in ("RewardConfig",):
+        from .train.config import RewardConfig
+        return RewardConfig
+    if name in ("RewardTrainer",):
+        from .train.reward import RewardTrainer
+        return RewardTrainer
     if name in ("SFTTrainer", "TrainOutput"):
         from .train import trainer
         return getattr(trainer, name)

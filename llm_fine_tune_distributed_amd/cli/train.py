@@ -24,22 +24,30 @@ def main(argv=None):
     from ..data.tokenizer import load_tokenizer
     from ..parallel.process_group import cleanup_distributed, setup_distributed
     from ..train import (AimCallback, DPOConfig, DPOTrainer, GKDConfig, GKDTrainer, GRPOConfig, GRPOTrainer,
-                         PerplexityCallback, SFTConfig, SFTTrainer, TrainingHistoryCallback, config_from_env)
+                         PerplexityCallback, RewardConfig, RewardTrainer, SFTConfig, SFTTrainer, TrainingHistoryCallback,
+                         config_from_env)
     from ..train.config import apply_overrides
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default=os.getenv("MODEL_NAME", "HuggingFaceTB/SmolLM3-3B"),
                     help="preset name or local HF directory (config.json + safetensors)")
-    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo", "gkd", "grpo"],
+    ap.add_argument("--trainer", default="sft", choices=["sft", "dpo", "gkd", "grpo", "reward"],
                     help="sft: supervised fine-tuning; dpo: preference training on {prompt, chosen, rejected} rows "
                          "(a preference JSONL / parquet through --dataset; --set beta=...); gkd: knowledge "
                          "distillation of --model from --teacher on the SFT data (--set beta=... temperature=...); "
-                         "grpo: reinforcement learning from --reward functions on the questions of the Q&A data "
-                         "(--set num_generations=... max_completion_length=...)")
+                         "grpo: reinforcement learning from --reward functions and / or --reward-model directories on "
+                         "the questions of the Q&A data (--set num_generations=... max_completion_length=...); "
+                         "reward: a reward model (score head in place of the LM head) on {chosen, rejected} rows "
+                         "with an optional prompt and margin (a preference JSONL / parquet through --dataset; "
+                         "--set center_rewards_coefficient=...)")
     ap.add_argument("--reward", dest="rewards", action="append", default=[], metavar="PKG.MODULE:FUNCTION",
                     help="--trainer grpo: a reward function f(prompts=, completions=, completion_ids=, **columns) -> "
                          "list[float] (repeatable; built in: llm_fine_tune_distributed_amd.train.rewards:answer_match "
                          "and :length_band)")
+    ap.add_argument("--reward-model", dest="reward_models", action="append", default=[], metavar="DIR",
+                    help="--trainer grpo: a reward model saved by --trainer reward (a one-label "
+                         "...ForSequenceClassification directory with the policy's vocabulary; repeatable; models "
+                         "come after the --reward functions in reward_weights' order)")
     ap.add_argument("--teacher", default=os.getenv("TEACHER_MODEL_NAME"),
                     help="--trainer gkd: the teacher, a preset name or local HF directory with the student's vocabulary")
     ap.add_argument("--dataset", default=os.getenv("DATASET_PATH", "data/qa_dataset.parquet"),
@@ -80,7 +88,7 @@ def main(argv=None):
     # dataset (training.py:155-212)
     if a.dataset != "synthetic" and os.path.exists(a.dataset):
         rows = load_qa_parquet(a.dataset) if a.dataset.endswith(".parquet") else load_jsonl(a.dataset)
-    elif a.trainer == "dpo":
+    elif a.trainer in ("dpo", "reward"):
         rows = synthetic_preferences(2845, seed=42)
     else:
         rows = generate_qa(2845, seed=42)
@@ -94,7 +102,7 @@ def main(argv=None):
                                           {"role": "user", "content": r["full-question"]}], "answer": r["answer"]}
         train_rows = [as_prompt(r) for r in train_rows]
         val_rows = [as_prompt(r) for r in val_rows]
-    elif a.trainer != "dpo":
+    elif a.trainer not in ("dpo", "reward"):
         train_rows = [format_prompt(r) for r in train_rows]
         val_rows = [format_prompt(r) for r in val_rows]
     tok_dir = a.model if os.path.isdir(a.model) else None
@@ -109,17 +117,18 @@ def main(argv=None):
         cap = float(os.environ["DDP_BUCKET_CAP_MB"]) if os.environ.get("DDP_BUCKET_CAP_MB") else None
         dist_args = dict(ddp_find_unused_parameters=False, ddp_bucket_cap_mb=cap, local_rank=st.local_rank)
     config_cls, trainer_cls = {"sft": (SFTConfig, SFTTrainer), "dpo": (DPOConfig, DPOTrainer),
-                               "gkd": (GKDConfig, GKDTrainer), "grpo": (GRPOConfig, GRPOTrainer)}[a.trainer]
+                               "gkd": (GKDConfig, GKDTrainer), "grpo": (GRPOConfig, GRPOTrainer),
+                               "reward": (RewardConfig, RewardTrainer)}[a.trainer]
     extra = {}
     if a.trainer == "grpo":
         from ..train.rewards import resolve
-        if not a.rewards:
-            ap.error("--trainer grpo needs at least one --reward pkg.module:function")
-        extra["reward_funcs"] = [resolve(r) for r in a.rewards]
+        if not a.rewards and not a.reward_models:
+            ap.error("--trainer grpo needs at least one --reward pkg.module:function or --reward-model DIR")
+        extra["reward_funcs"] = [resolve(r) for r in a.rewards] + list(a.reward_models)
         # batches count completions (whole groups of num_generations); the best model is the best eval_reward
         dist_args = dict(dist_args, metric_for_best_model="eval_reward", greater_is_better=True)
-    elif a.rewards:
-        ap.error("--reward belongs to --trainer grpo")
+    elif a.rewards or a.reward_models:
+        ap.error("--reward and --reward-model belong to --trainer grpo")
     if a.trainer == "gkd":
         if not a.teacher:
             ap.error("--trainer gkd needs --teacher (a preset name or local HF directory)")

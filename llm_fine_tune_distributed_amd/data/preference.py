@@ -6,6 +6,10 @@ preference format: ``prompt`` a list of messages, ``chosen`` / ``rejected`` the 
 rendered through the chat template with the generation prompt; prompt and completion are tokenised SEPARATELY and the
 ids concatenated (TRL ``tokenize_row``), EOS appended when the completion does not end with it — so both sequences
 of a pair start with the same prompt ids and ``loss_start = len(prompt_ids)``.
+
+Reward modelling (train/reward.py) reads the same rows, and also rows without ``"prompt"`` (TRL's implicit-prompt
+format: ``chosen`` / ``rejected`` are whole texts or whole conversations) and a numeric ``"margin"`` column, which the
+collator carries per pair (``preference_margins``).
 """
 from __future__ import annotations
 
@@ -38,6 +42,20 @@ def tokenize_preference_rows(rows: Sequence[Dict], tokenizer, max_length: Option
     eos = tokenizer.eos_token_id
     seqs, starts = [], []
     for r in rows:
+        if "prompt" not in r:
+            # TRL's implicit-prompt format (reward modelling): each side is a whole conversation. A string is tokenised
+            # as it stands plus EOS, a message list through the chat template without the generation prompt; there
+            # is no prompt to mask (loss_start 0)
+            for key in ("chosen", "rejected"):
+                v = r[key]
+                ids = tokenizer.encode(v if isinstance(v, str) else tokenizer.apply_chat_template(list(v), tokenize=False))
+                if isinstance(v, str) and eos is not None and (not ids or ids[-1] != eos):
+                    ids = ids + [eos]
+                if max_length:
+                    ids = ids[:int(max_length)]
+                seqs.append(ids)
+                starts.append(0)
+            continue
         pm = _prompt_messages(r["prompt"])
         ptext = tokenizer.apply_chat_template(pm, tokenize=False, add_generation_prompt=True)
         pids = tokenizer.encode(ptext)
@@ -72,9 +90,10 @@ class PreferenceCollator(SFTCollator):
     reference log-probabilities. ``num_tokens`` counts both sequences. Always padding-free, on CPU too."""
 
     def __init__(self, pad_token_id: int, pad_to_multiple_of: Optional[int] = None,
-                 ref_logps: Optional[torch.Tensor] = None):
+                 ref_logps: Optional[torch.Tensor] = None, margins: Optional[torch.Tensor] = None):
         super().__init__(pad_token_id, pad_to_multiple_of, None, packing=True, max_tokens=None)
         self.ref_logps = ref_logps
+        self.margins = margins  # [N], one per pair (reward modelling): the batch's are b["margins"]
 
     def __call__(self, ds: TokenizedDataset, indices: torch.Tensor) -> Dict:
         pairs = indices.to(torch.int64).reshape(-1)
@@ -85,4 +104,14 @@ class PreferenceCollator(SFTCollator):
         b.update(n_seqs=2 * B, num_items=B, num_samples=B)
         if self.ref_logps is not None:
             b["ref_logps"] = self.ref_logps[idx].to(torch.float32)
+        if self.margins is not None:
+            b["margins"] = self.margins[pairs].to(torch.float32)
         return b
+
+
+def preference_margins(rows: Sequence[Dict]) -> Optional[torch.Tensor]:
+    """fp32 [N]: the rows' numeric ``"margin"`` column (TRL ``RewardTrainer``; a row without one counts 0), or None
+    when no row has it."""
+    if not any("margin" in r and r["margin"] is not None for r in rows):
+        return None
+    return torch.tensor([float(r.get("margin") or 0.0) for r in rows], dtype=torch.float32)

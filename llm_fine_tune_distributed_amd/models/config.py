@@ -49,6 +49,9 @@ class ModelConfig:
     # itself (transformers' sliding_window_overlay). None: full causal attention. Every layer has the same window;
     # each Attention module reads its own (Attention.window), so a per-layer list would only change that one read.
     sliding_window: Optional[int] = None
+    # Sequence classification: None is the causal LM; 1 is a reward model, the trunk plus a ``score`` head [1, hidden]
+    # and no LM head (HF ``...ForSequenceClassification`` with one label). No other value is accepted.
+    num_labels: Optional[int] = None
     extra: Dict[str, Any] = field(default_factory=dict)
 
     def __post_init__(self):
@@ -72,6 +75,10 @@ class ModelConfig:
             if self.sliding_window <= 0:
                 raise ValueError(f"sliding_window must be a positive number of keys or None, got {self.sliding_window}")
         assert self.num_attention_heads % self.num_key_value_heads == 0
+        if self.num_labels is not None and int(self.num_labels) != 1:
+            raise ValueError(f"num_labels must be None (causal LM) or 1 (reward model), got {self.num_labels}")
+        if self.num_labels is not None:
+            self.num_labels = 1
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -163,6 +170,13 @@ class ModelConfig:
         if self.model_type == "qwen2":
             del d["mlp_bias"], d["attention_bias"]  # not Qwen2Config keys: the q / k / v biases are unconditional
             d["use_sliding_window"] = False
+        if self.num_labels is not None:
+            # a reward model: the model type's sequence-classification class with one label; transformers needs a pad
+            # token to find each row's last token
+            d["architectures"] = [arch.replace("ForCausalLM", "ForSequenceClassification")]
+            d["num_labels"] = 1
+            if d["pad_token_id"] is None:
+                d["pad_token_id"] = self.eos_token_id if self.eos_token_id is not None else 0
         d.update(self.extra)
         return d
 
@@ -184,6 +198,14 @@ class ModelConfig:
             kw["model_type"] = "llama"  # (mistral among them: Llama's weights plus sliding_window, read below)
         mt = kw["model_type"]
         kw.pop("sliding_window", None)
+        kw.pop("num_labels", None)
+        if any(str(a).endswith("ForSequenceClassification") for a in (d.get("architectures") or [])):
+            # (transformers writes id2label in place of num_labels)
+            n = d.get("num_labels", len(d["id2label"]) if d.get("id2label") else None)
+            if n is None or int(n) != 1:
+                raise NotImplementedError(f"sequence classification with num_labels={n}: only one-label reward models "
+                                          "are supported")
+            kw["num_labels"] = 1
         if mt == "llama":
             # Mistral: sliding_window (missing or null: full attention). One window for every layer: a layer_types
             # list may only repeat one type.

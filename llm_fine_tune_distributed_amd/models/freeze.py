@@ -26,7 +26,9 @@ def apply_freeze_policy(model, policy: str = "full", n_last: int = 2, lora_confi
             layers = model.model.layers
             for p in layers[-n_last:].parameters():
                 p.requires_grad_(True)
-            model.lm_head_weight.requires_grad_(True)
+            # the output head: a reward model's score head stands in place of the LM head
+            head = model.score if getattr(model, "score", None) is not None else model.lm_head_weight
+            head.requires_grad_(True)
         except Exception:  # reference falls back to all-trainable on any error (training.py:143-145)
             for p in model.parameters():
                 p.requires_grad_(True)

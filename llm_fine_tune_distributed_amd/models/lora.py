@@ -74,6 +74,10 @@ def apply_lora(model, cfg: LoRAConfig = None):
     mc = model.config
     for p in model.parameters():
         p.requires_grad_(False)
+    if getattr(model, "score", None) is not None:
+        # a reward model's head is new, not pretrained: it trains next to the adapters (PEFT's modules_to_save for
+        # task_type SEQ_CLS) and is saved with the base weights
+        model.score.requires_grad_(True)
     t = set(cfg.target_modules)
     ref_w = model.model.embed_tokens
     dev, dt = ref_w.device, ref_w.dtype

@@ -195,7 +195,12 @@ class CausalLM(nn.Module):
         super().__init__()
         self.config = cfg
         self.model = Model(cfg)
-        if cfg.tie_word_embeddings:
+        # a reward model (cfg.num_labels == 1; HF ...ForSequenceClassification): the trunk plus score [1, hidden], no
+        # LM head at all, tied or not — sequence_scores is its one output
+        self.score = None
+        if cfg.num_labels is not None:
+            self.score = nn.Parameter(torch.empty(1, cfg.hidden_size))
+        if cfg.tie_word_embeddings or cfg.num_labels is not None:
             self.lm_head = None
         else:
             self.lm_head = nn.Parameter(torch.empty(cfg.vocab_size, cfg.hidden_size))
@@ -211,12 +216,22 @@ class CausalLM(nn.Module):
     # ------------------------------------------------------------------ params
     @property
     def lm_head_weight(self) -> torch.Tensor:
+        self._refuse_reward_model("the LM head")
         return self.model.embed_tokens if self.lm_head is None else self.lm_head
+
+    @property
+    def is_reward_model(self) -> bool:
+        return self.score is not None
+
+    def _refuse_reward_model(self, what: str) -> None:
+        if self.score is not None:
+            raise RuntimeError(f"{what} on a reward model (num_labels=1): it has a score head and no LM head; use "
+                               "sequence_scores")
 
     def _declare_uses(self):
         for p in self.parameters():
             p._sftamd_uses = 1
-        if self.lm_head is None:
+        if self.lm_head is None and self.score is None:
             self.model.embed_tokens._sftamd_uses = 2
 
     def reset_grad_use_counters(self):
@@ -325,6 +340,7 @@ class CausalLM(nn.Module):
         mean over valid tokens when ``num_items_in_batch`` is None. ``label_smoothing`` (HF ``LabelSmoother``) and
         ``loss_type="dft"`` (TRL ``dft_loss``) change the per-token objective inside the fused cross-entropy.
         """
+        self._refuse_reward_model("forward (a language-model loss or logits)")
         dev = input_ids.device
         h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
 
@@ -356,9 +372,41 @@ class CausalLM(nn.Module):
         return ops.lm_head_seq_logps(h, self.lm_head_weight, labels, cu_seqlens, int(n_seqs))
 
     def _refuse_cp(self, what: str) -> None:
+        self._refuse_reward_model(what)
         if len(self.model.layers) and self.model.layers[0].self_attn.cp_group is not None:
             raise NotImplementedError(f"{what} under context parallelism: a sequence's label rows are spread over "
                                       "the group's ranks and the per-sequence sum is not reduced across them")
+
+    def sequence_scores(self, input_ids: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                        position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
+                        n_seqs: Optional[int] = None, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A reward model's scores, fp32 [n_seqs], differentiable: the final hidden state of each sequence's LAST token
+        times the ``score`` head (``ops.seq_score``; HF ``...ForSequenceClassification`` logits[:, 0]). Padding-free
+        ``input_ids`` [M] with ``cu_seqlens`` score the first ``n_seqs`` segments (default: all of them). A padded
+        (right) [B, T] batch scores column ``lengths[b] - 1`` of row b (default T - 1): the same op over a cu_seqlens
+        built from the lengths, attention still running over the whole rows. The trunk is ``forward``'s."""
+        if self.score is None:
+            raise RuntimeError("sequence_scores needs a reward model: build it with num_labels=1 (it has a score head "
+                               "in place of the LM head)")
+        if len(self.model.layers) and self.model.layers[0].self_attn.cp_group is not None:
+            raise NotImplementedError("sequence_scores under context parallelism: a sequence's last row lives on one "
+                                      "rank of the group and the score is not shared across them")
+        padded = input_ids.dim() == 2 and cu_seqlens is None
+        if lengths is not None and not padded:
+            raise ValueError("lengths go with a padded [B, T] batch; a padding-free batch has cu_seqlens")
+        h, _, cu = self._hidden(input_ids, None, cu_seqlens, max_seqlen, position_ids, False)
+        if padded and lengths is not None:
+            B, T = input_ids.shape
+            # a non-decreasing cu over the B T rows: segment 2b = row b's tokens [b T, b T + len_b), segment 2b + 1 =
+            # its padding; the even segments are the scores (a zero length scores +0)
+            ln = lengths.to(device=h.device, dtype=torch.int64).clamp(0, T)
+            start = torch.arange(B, device=h.device, dtype=torch.int64) * T
+            cu2 = torch.stack([start, start + ln], dim=1).reshape(-1)
+            cu2 = torch.cat([cu2, cu2.new_full((1,), B * T)]).to(torch.int32)
+            return ops.seq_score(h, self.score, cu2, 2 * B)[0::2]
+        if n_seqs is None:
+            n_seqs = cu.numel() - 1
+        return ops.seq_score(h, self.score, cu, int(n_seqs))
 
     def policy_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, advantages: torch.Tensor,
                     cu_seqlens: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
@@ -399,6 +447,7 @@ class CausalLM(nn.Module):
         """The logits of every token row, [M, vocab] in the model's dtype (M = B x T of a padded batch, pads included),
         without an autograd graph through the LM head: what a distillation teacher hands to the student's
         ``distill_loss`` (call it under ``torch.no_grad()``). The trunk is ``forward``'s."""
+        self._refuse_reward_model("logits_rows")
         h, _, _ = self._hidden(input_ids, None, cu_seqlens, max_seqlen, position_ids, False)
         return ops.lm_head_logits(h, self.lm_head_weight)
 
@@ -412,6 +461,7 @@ class CausalLM(nn.Module):
         cross-entropy. ``teacher_logits`` [M, vocab] are a teacher's ``logits_rows`` of the same batch. ``stats`` is
         [5, M] (loss, student lse, teacher lse, correct, agrees with the teacher's argmax) and ``metrics`` =
         [correct, teacher-agreement count, valid]."""
+        self._refuse_reward_model("distill_loss")
         dev = input_ids.device
         h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
         valid = labels != -100
@@ -506,6 +556,8 @@ class CausalLM(nn.Module):
         sd["model.norm.weight"] = self.model.norm.weight.detach()
         if self.lm_head is not None:
             sd["lm_head.weight"] = self.lm_head.detach()
+        if self.score is not None:
+            sd["score.weight"] = self.score.detach()
         return sd
 
     @torch.no_grad()
@@ -538,6 +590,9 @@ class CausalLM(nn.Module):
         self.model.norm.weight.copy_(take("model.norm.weight"))
         if self.lm_head is not None:
             self.lm_head.copy_(take("lm_head.weight"))
+        if self.score is not None and "score.weight" in sd:
+            # (a causal-LM state dict has none: the head keeps its initialisation, the LM head is dropped below)
+            self.score.copy_(take("score.weight"))
         extra = set(sd) - used - {"lm_head.weight"}
         if strict and extra:
             raise KeyError(f"unexpected keys: {sorted(extra)[:8]}")

@@ -514,3 +514,96 @@ def scale_rows(x: torch.Tensor, coef: torch.Tensor, gscale: torch.Tensor) -> tor
     ct = torch.float64 if x.dtype == torch.float64 else torch.float32
     c = coef.to(ct) * gscale.to(ct).reshape(())
     return (x.to(ct) * c[:, None]).to(x.dtype)
+
+
+# ----------------------------------------------------------------------------- reward modelling (csrc/reward.hip)
+def _last_rows(M: int, cu_seqlens: torch.Tensor, n_seqs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(last int64 [n_seqs], nonempty bool [n_seqs]): segment s is [a, b) with a = clamp(cu[s], 0, M), b =
+    clamp(cu[s + 1], a, M); its last row is b - 1 (0 where the segment is empty)."""
+    cu = cu_seqlens[:n_seqs + 1].to(torch.int64)
+    a = cu[:-1].clamp(0, M)
+    b = torch.minimum(torch.maximum(cu[1:], a), torch.tensor(M, dtype=torch.int64, device=cu.device))
+    nonempty = b > a
+    return torch.where(nonempty, b - 1, torch.zeros_like(b)), nonempty
+
+
+def _lane_dot(prod: torch.Tensor) -> torch.Tensor:
+    """The row sums of ``prod`` [S, H] (H a multiple of 8) in seq_score_fwd's order: lane l of 64 adds the elements of
+    the 8-wide chunks l, l + 64, ... in element order, then the xor butterfly 32, 16, ..., 1 over the lanes."""
+    S, H = prod.shape
+    nc = H // 8
+    passes = (nc + 63) // 64
+    p = torch.zeros(S, passes * 64 * 8, dtype=prod.dtype, device=prod.device)
+    p[:, :H] = prod
+    p = p.view(S, passes, 64, 8)
+    acc = torch.zeros(S, 64, dtype=prod.dtype, device=prod.device)
+    for k in range(passes):
+        for i in range(8):
+            acc = acc + p[:, k, :, i]
+    lanes = torch.arange(64, device=prod.device)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lanes ^ o]
+    return acc[:, 0]
+
+
+def seq_score(h: torch.Tensor, w: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int) -> torch.Tensor:
+    """scores[s] = h[last row of segment s] . w for the first ``n_seqs`` segments of ``cu_seqlens`` (an empty one
+    gives +0; later segments, the collators' pad, are ignored) — twin of csrc/reward.hip seq_score_fwd with its
+    summation order, in fp32 (fp64 operands stay fp64)."""
+    ct = torch.float64 if h.dtype == torch.float64 else torch.float32
+    M, H = h.shape
+    if H % 8:
+        raise ValueError(f"seq_score: H must be a multiple of 8, got {H}")
+    if n_seqs == 0:
+        return torch.zeros(0, dtype=ct, device=h.device)
+    last, nonempty = _last_rows(M, cu_seqlens.to(h.device), n_seqs)
+    if M == 0:
+        return torch.zeros(n_seqs, dtype=ct, device=h.device)
+    dots = _lane_dot(h[last].to(ct) * w.reshape(1, -1).to(ct))
+    return torch.where(nonempty, dots, torch.zeros_like(dots))
+
+
+def seq_score_bwd(g: torch.Tensor, h: torch.Tensor, w: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int,
+                  need_dh: bool = True, need_dw: bool = True):
+    """(dh in h's dtype [M, H], dw fp32 [H]; None for the half not needed) — twin of csrc/reward.hip seq_score_bwd,
+    bit-equal on bf16. dh is +0 except the last row of each non-empty segment, g_s * w in one product and one
+    rounding; dw[j] = sum over the non-empty segments in increasing s of g_s * h[last_s, j]."""
+    ct = torch.float64 if h.dtype == torch.float64 else torch.float32
+    M, H = h.shape
+    last, nonempty = _last_rows(M, cu_seqlens.to(h.device), n_seqs)
+    gs, wf = g.to(ct), w.reshape(-1).to(ct)
+    dh = dw = None
+    if need_dh:
+        dh = torch.zeros_like(h)
+        if M:
+            dh[last[nonempty]] = (gs[nonempty, None] * wf[None, :]).to(h.dtype)
+    if need_dw:
+        dw = torch.zeros(H, dtype=ct, device=h.device)
+        for s in torch.nonzero(nonempty).reshape(-1).tolist() if M else []:
+            dw = dw + gs[s] * h[last[s]].to(ct)
+    return dh, dw
+
+
+def reward_pair(scores: torch.Tensor, margins: Optional[torch.Tensor], inv_pairs: torch.Tensor,
+                center_coef: float = 0.0) -> torch.Tensor:
+    """The pairwise reward-model loss (TRL ``RewardTrainer``), score 2p chosen and 2p + 1 rejected — twin of
+    csrc/reward.hip reward_pair_fwd. With z = (r_c - r_r) - margin and c = ``center_coef``, stats [4, P] in the scores'
+    dtype: softplus(-z) + c (r_c + r_r)^2 with softplus as max(-z, 0) + log1p(exp(-|z|)); d(inv_pairs sum loss) / d
+    r_c = (-sigmoid(-z) + 2 c (r_c + r_r)) inv_pairs; the same / d r_r = (sigmoid(-z) + 2 c (r_c + r_r)) inv_pairs; z.
+    With c == 0 the centring terms are not formed: row 2 is the exact negation of row 1."""
+    dt = scores.dtype
+    rc, rr = scores[0::2], scores[1::2]
+    z = rc - rr
+    z = z - (margins.to(dt) if margins is not None else torch.zeros_like(z))
+    e = torch.exp(-z.abs())
+    loss = (-z).clamp(min=0) + torch.log1p(e)
+    sig = torch.where(z >= 0, e, torch.ones_like(e)) / (1 + e)
+    gc, gr = -sig, sig
+    c = torch.tensor(float(center_coef), dtype=torch.float32).to(dt)  # the kernel's fp32 coefficient
+    if float(center_coef) != 0.0:
+        total = rc + rr
+        tc = (2 * c) * total
+        loss = loss + c * (total * total)
+        gc, gr = gc + tc, gr + tc
+    inv = inv_pairs.to(dt).reshape(())
+    return torch.stack([loss, gc * inv, gr * inv, z])

@@ -326,7 +326,9 @@ class DDPEngine:
         # rank order; the tied weight is then updated on every rank (replicated, no ZeRO all-gather).
         tied_w = None
         inner = getattr(model, "model", None)
-        if getattr(model, "lm_head", 0) is None and inner is not None and hasattr(inner, "embed_tokens"):
+        # (a reward model has no LM head at all: its embedding has the one sparse use, so nothing is tied)
+        if getattr(model, "lm_head", 0) is None and getattr(model, "score", None) is None and inner is not None \
+                and hasattr(inner, "embed_tokens"):
             tied_w = inner.embed_tokens if inner.embed_tokens.requires_grad else None
         if tied_sparse is None:
             tied_sparse = os.environ.get("SFTAMD_TIED_SPARSE", "1") == "1"

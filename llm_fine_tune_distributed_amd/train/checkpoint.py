@@ -12,6 +12,7 @@
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 import random
@@ -128,7 +129,9 @@ def save_pretrained(model, path: str, tokenizer=None, max_shard_size: int = 5 * 
         if lc is not None:
             with open(os.path.join(tmp, "adapter_config.json"), "w") as f:
                 json.dump({"peft_type": "LORA", "r": lc.r, "lora_alpha": lc.lora_alpha, "lora_dropout": lc.lora_dropout,
-                           "target_modules": lc.target_modules, "task_type": "CAUSAL_LM"}, f, indent=2)
+                           "target_modules": lc.target_modules,
+                           "task_type": "SEQ_CLS" if getattr(model, "score", None) is not None else "CAUSAL_LM"},
+                          f, indent=2)
     model.config.save_pretrained(tmp)
     gc = dict(GEN_CONFIG)
     gc.update({"eos_token_id": model.config.eos_token_id, "bos_token_id": model.config.bos_token_id,
@@ -140,10 +143,16 @@ def save_pretrained(model, path: str, tokenizer=None, max_shard_size: int = 5 * 
     _commit_dir(tmp, path)
 
 
-def from_pretrained(path: str, device="cpu", dtype=torch.bfloat16):
+def from_pretrained(path: str, device="cpu", dtype=torch.bfloat16, num_labels: Optional[int] = None, seed: int = 0):
+    """The model of the HF directory ``path``: a causal LM, or a reward model when its config.json is a one-label
+    ``...ForSequenceClassification``. ``num_labels=1`` reads a causal-LM directory as a reward model: the trunk's
+    weights, ``lm_head.weight`` dropped, and a fresh score head drawn normal(0, initializer_range) from ``seed`` (the
+    same on every rank), as transformers initialises a new head."""
     from ..models import ModelConfig, build_model
     cfg = ModelConfig.from_pretrained(path)
-    m = build_model(cfg, device=device, dtype=dtype)
+    if num_labels is not None:
+        cfg = dataclasses.replace(cfg, num_labels=num_labels)
+    m = build_model(cfg, device=device, dtype=dtype, seed=seed)
     m.load_hf_state_dict({k: v.to(dtype) for k, v in load_state_dict(path, device).items()}, strict=False)
     return m
 

@@ -467,6 +467,41 @@ class GRPOConfig(SFTConfig):
 GRPOConfig.__init__ = _tolerant_init(GRPOConfig.__init__)
 
 
+@dataclass
+class RewardConfig(SFTConfig):
+    """``SFTConfig`` plus TRL's ``RewardConfig`` fields for reward modelling on preference pairs (train/reward.py).
+    Batches are always padding-free; ``max_length`` (default 1024) cuts each sequence's tail."""
+    learning_rate: float = 1e-4             # TRL RewardConfig's default
+    center_rewards_coefficient: Optional[float] = None  # None: 0; weight of (r_chosen + r_rejected)^2
+
+    def __post_init__(self):
+        self.validate_objective()
+
+    def validate_objective(self) -> None:
+        a = self.neftune_noise_alpha
+        if a is not None and not float(a) >= 0:
+            raise ValueError(f"neftune_noise_alpha must be None or >= 0, got {a}")
+        if self.loss_type != "nll":
+            raise ValueError(f"RewardConfig: loss_type={self.loss_type!r} selects a per-token objective; the reward "
+                             "model's loss is the pairwise logistic loss (leave loss_type at 'nll')")
+        if float(self.label_smoothing_factor) != 0.0:
+            raise ValueError("RewardConfig: label_smoothing_factor smooths a per-token cross-entropy; the pairwise "
+                             "loss has none")
+        if self.packing:
+            raise ValueError("RewardConfig: packing=True is not supported (batches of pairs are padding-free already)")
+        if int(self.context_parallel_size or 1) > 1:
+            raise ValueError("RewardConfig: context_parallel_size > 1 is not supported (a sequence's last row lives on "
+                             "one rank of a context-parallel group)")
+        c = self.center_rewards_coefficient
+        if c is not None and not float(c) >= 0:
+            raise ValueError(f"RewardConfig: center_rewards_coefficient must be None or >= 0, got {c}")
+        if self.max_length is not None and int(self.max_length) < 1:
+            raise ValueError(f"RewardConfig: max_length must be None or >= 1, got {self.max_length}")
+
+
+RewardConfig.__init__ = _tolerant_init(RewardConfig.__init__)
+
+
 def config_from_env(base: Optional[SFTConfig] = None, world_size: int = 1) -> Dict[str, Any]:
     """The reference's env contract (training.py:56-60,240): EPOCHS, BATCH_SIZE, LEARNING_RATE,
     DATA_DIR, OUTPUT_DIR, AIM_REPO. Returns the resolved values (LR scaled by world size like
