@@ -96,6 +96,13 @@ TORCH_LIBRARY(sftamd, m) {
   // lse, teacher lse, student argmax == label, student argmax == teacher argmax); write_grad leaves the gradient
   // over student_logits
   m.def("kd_fwd(Tensor(a!) student_logits, Tensor teacher_logits, Tensor labels, Tensor inv_count, bool write_grad, float beta, float temperature) -> Tensor");
+  // offline distillation (csrc/distill_topk.hip): the k largest logits per row, value descending and equal values by
+  // column ascending, as (int32 ids [M, k], fp32 log softmax(x / tau) there, the lse over the whole row); and the
+  // forward KL of the student against such a truncated teacher: stats [5, M] = (loss, student lse, teacher mass kept,
+  // student argmax == label, student argmax == ids[:, 0]); write_grad leaves the gradient over student_logits. The ids
+  // of a row are distinct and in [0, vocab)
+  m.def("teacher_topk(Tensor logits, int k, float temperature) -> (Tensor, Tensor)");
+  m.def("kd_topk_fwd(Tensor(a!) student_logits, Tensor ids, Tensor logps, Tensor labels, Tensor inv_count, bool write_grad, float temperature) -> Tensor");
   // sequence-level objectives (csrc/preference.hip): logps[s] = -sum nll[cu[s] : cu[s + 1]]; rows of sequence s times
   // coef[s] * gscale (rows at or past cu[n_seqs]: 0; csrc/scale_rows.hip); DPO per-pair stats [5, P] = (loss, coef, reward_c, reward_r, delta)
   m.def("seq_logp_sum(Tensor nll, Tensor cu_seqlens, int n_seqs) -> Tensor");

@@ -71,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--set", dest="sets", action="append", default=[], metavar="FIELD=VALUE",
                     help="override one SFTConfig field (repeatable; highest precedence), e.g. "
                          "neftune_noise_alpha=5, label_smoothing_factor=0.1 or loss_type=dft")
+    ap.add_argument("--precompute-only", action="store_true",
+                    help="--trainer gkd with teacher_topk=K: write the teacher's top-k cache "
+                         "(checkpoints/teacher_topk-<fingerprint>.pt) and stop; later runs need no --teacher")
     ap.add_argument("--merge-lora", action="store_true",
                     help="LoRA runs: write best_model/ with the adapters merged into the weights")
     a = ap.parse_args(argv)
@@ -130,11 +133,12 @@ def main(argv=None):
     elif a.rewards or a.reward_models:
         ap.error("--reward and --reward-model belong to --trainer grpo")
     if a.trainer == "gkd":
-        if not a.teacher:
-            ap.error("--trainer gkd needs --teacher (a preset name or local HF directory)")
-        dist_args = dict(dist_args, teacher_model_name_or_path=a.teacher)
+        if a.teacher:
+            dist_args = dict(dist_args, teacher_model_name_or_path=a.teacher)
     elif a.teacher:
         ap.error("--teacher belongs to --trainer gkd")
+    if a.precompute_only and a.trainer != "gkd":
+        ap.error("--precompute-only belongs to --trainer gkd with --set teacher_topk=K")
     args = config_cls(
         output_dir=f"{out}/checkpoints", per_device_train_batch_size=env["batch_size"],
         per_device_eval_batch_size=env["batch_size"], gradient_accumulation_steps=a.grad_accum,
@@ -149,12 +153,24 @@ def main(argv=None):
         log_step_phases=a.log_step_phases, log_system_metrics_every=a.log_system_metrics_every,
         **{"metric_for_best_model": "eval_loss", "greater_is_better": False, **dist_args})
     args = apply_overrides(args, a.config, a.sets)
+    if a.trainer == "gkd":
+        # with teacher_topk a cache file written earlier stands in for the teacher (GKDTrainer checks that it is there)
+        if not a.teacher and args.teacher_topk is None:
+            ap.error("--trainer gkd needs --teacher (a preset name or local HF directory)")
+        if a.precompute_only and args.teacher_topk is None:
+            ap.error("--precompute-only needs --set teacher_topk=K")
     if st.is_main:  # the resolved configuration of this run, next to its artifacts
         args.to_json(f"{out}/sft_config.json")
     trainer = trainer_cls(model=a.model, args=args, train_dataset=train_rows, eval_dataset=val_rows,
                          processing_class=tokenizer, callbacks=[history, ppl, aim], **extra)
     if st.device.type == "cuda" and st.is_main:
         print(f"VRAM after model load: {torch.cuda.memory_allocated() / 2**30:.2f} GB allocated")
+    if a.precompute_only:
+        trainer.precompute_teacher_topk()
+        if st.is_main:
+            print(f"teacher top-k cache: {trainer.teacher_topk_path()}")
+        cleanup_distributed()
+        return
     result = trainer.train(resume_from_checkpoint=a.resume)
 
     trainer.save_model(f"{out}/best_model", merge_lora=a.merge_lora)  # rank 0 writes, all ranks barrier

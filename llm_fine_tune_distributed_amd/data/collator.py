@@ -4,6 +4,7 @@
   pads -> -100, ``num_items`` = non-ignored *shifted* label count (HF ``num_items_in_batch``);
   or padding-free packing (varlen ``cu_seqlens``/``position_ids``, numerically identical per
   sample, no pad FLOPs). Both call the native CPU kernels of ``csrc/data_pipeline.cpp``.
+* ``DistillTopKCollator``: ``SFTCollator`` plus the rows of a teacher's cached top-k log-probabilities.
 * ``DistributedBatchSampler``: Accelerate ``BatchSamplerShard`` semantics — the base sampler is
   a seeded shuffle reshuffled every epoch; rank r takes batches r, r+W, r+2W, ...; drop_last
   keeps every rank's batch count equal (C11: no communication).
@@ -89,6 +90,51 @@ class SFTCollator:
         return {"input_ids": ids, "labels": labels, "cu_seqlens": cu, "position_ids": pos,
                 "max_seqlen": int(lens.max()), "num_items": int((labels != -100).sum()), "num_samples": n,
                 "num_tokens": int(cu[n]) if n < cu.numel() else int(cu[-1]), "shifted": True}
+
+
+class DistillTopKCollator(SFTCollator):
+    """``SFTCollator`` that carries a teacher's cached top-k log-probabilities (``GKDTrainer``, ``teacher_topk``) as
+    ``PreferenceCollator`` carries ``ref_logps``: ``teacher_ids`` int32 / ``teacher_logps`` fp32 hold one row per stored
+    token of the dataset, the row of sample i at position j being ``offsets[i] + j``. A batch gets the rows of its
+    tokens: [M, k] packed / padding-free, [B, T, k] padded; pad rows hold id 0 and log-probability 0 (their label is
+    -100). Truncation (``max_length``, a packed sample cut at ``max_tokens``) keeps a sample's first rows, and samples a
+    full pack left out get none, because the rows follow the batch's own lengths."""
+
+    teacher_ids: Optional[torch.Tensor] = None
+    teacher_logps: Optional[torch.Tensor] = None
+
+    def _rows(self, src: torch.Tensor, shape) -> torch.Tensor:
+        """src [n] = the cache row of every batch position, -1 for a pad -> (ids, logps) of ``shape`` + [k]."""
+        if self.teacher_ids is None or self.teacher_logps is None:
+            raise RuntimeError("DistillTopKCollator: the teacher's top-k cache is not attached yet")
+        pad = src < 0
+        src = src.clamp(min=0)
+        ids = self.teacher_ids[src].masked_fill(pad[:, None], 0)
+        lps = self.teacher_logps[src].masked_fill(pad[:, None], 0.0)
+        k = ids.shape[-1]
+        return ids.reshape(*shape, k), lps.reshape(*shape, k)
+
+    def _pad(self, ds, idx):
+        b = super()._pad(ds, idx)
+        B, T = b["input_ids"].shape
+        lens = ds.lengths()[idx].clamp(max=T)
+        if self.max_length:
+            lens = lens.clamp(max=self.max_length)
+        pos = torch.arange(T)[None, :]
+        src = torch.where(pos < lens[:, None], ds.offsets[idx][:, None] + pos, torch.full((B, T), -1))
+        b["teacher_ids"], b["teacher_logps"] = self._rows(src.reshape(-1), (B, T))
+        return b
+
+    def _pack(self, ds, idx):
+        b = super()._pack(ds, idx)
+        cu = b["cu_seqlens"].to(torch.int64)
+        M = b["input_ids"].numel()
+        src = torch.full((M,), -1, dtype=torch.int64)
+        for s in range(b["num_samples"]):  # segment s holds the first cu[s + 1] - cu[s] tokens of sample idx[s]
+            a, e = int(cu[s]), int(cu[s + 1])
+            src[a:e] = int(ds.offsets[idx[s]]) + torch.arange(e - a)
+        b["teacher_ids"], b["teacher_logps"] = self._rows(src, (M,))
+        return b
 
 
 def _pad_py(ds, idx, pad_id, mult, max_length):

@@ -38,6 +38,7 @@ class CausalLMOutput:
     metrics: Optional[torch.Tensor] = None
     rows: Optional[torch.Tensor] = None   # policy_loss: [2, M] per-row loss and coefficient
     seq: Optional[torch.Tensor] = None    # policy_loss: [6, S] per-sequence sums
+    teacher_mass: Optional[torch.Tensor] = None  # distill_topk_loss: the kept teacher mass summed over the valid rows
 
 
 class RMSNorm(nn.Module):
@@ -473,9 +474,46 @@ class CausalLM(nn.Module):
         out.metrics = torch.stack([out.stats[3].sum(), out.stats[4].sum(), out.num_tokens])
         return out
 
+    def topk_logps_rows(self, input_ids: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                        position_ids: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None, k: int = 64,
+                        temperature: float = 1.0):
+        """A teacher's top-``k`` token log-probabilities of every token row, (ids int32 [M, k], logps fp32 [M, k])
+        with M as in ``logits_rows``: the k largest logits (value descending, equal values by column ascending) and
+        log softmax(logits / temperature) there. What offline distillation caches and the student's
+        ``distill_topk_loss`` consumes (call it under ``torch.no_grad()``). The trunk is ``forward``'s."""
+        self._refuse_cp("topk_logps_rows")
+        h, _, _ = self._hidden(input_ids, None, cu_seqlens, max_seqlen, position_ids, False)
+        return ops.lm_head_topk_logps(h, self.lm_head_weight, int(k), temperature)
+
+    def distill_topk_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, teacher_ids: torch.Tensor,
+                          teacher_logps: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None,
+                          max_seqlen: Optional[int] = None, position_ids: Optional[torch.Tensor] = None,
+                          num_items_in_batch=None, shift_labels: bool = True, temperature: float = 1.0,
+                          **_) -> CausalLMOutput:
+        """Offline knowledge distillation: the forward KL(teacher || student) over the teacher's top-k support, not
+        renormalised, from a teacher's cached ``topk_logps_rows`` of the same batch (``teacher_ids`` int32 and
+        ``teacher_logps`` fp32, [M, k] or [B, T, k]) at the same ``temperature``. Rows, normalisation, ``stats`` layout
+        and ``metrics`` are ``distill_loss``'s, with the teacher mass kept in ``stats[2]`` and the teacher's first
+        cached id in the agreement count."""
+        self._refuse_cp("distill_topk_loss")
+        dev = input_ids.device
+        h, labels, _ = self._hidden(input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels)
+        valid = labels != -100
+        inv = _inv_count(num_items_in_batch, valid, dev)
+        out = CausalLMOutput()
+        k = teacher_ids.shape[-1]
+        out.loss, out.stats = ops.lm_head_distill_topk_loss(h, self.lm_head_weight, teacher_ids.reshape(-1, k),
+                                                            teacher_logps.reshape(-1, k), labels, inv, temperature)
+        vf = valid.float()
+        out.num_tokens = vf.sum()
+        out.metrics = torch.stack([out.stats[3].sum(), out.stats[4].sum(), out.num_tokens])
+        out.teacher_mass = (out.stats[2] * vf).sum()
+        return out
+
     def _hidden(self, input_ids, labels, cu_seqlens, max_seqlen, position_ids, shift_labels):
-        """The trunk shared by ``forward``, ``sequence_logps``, ``policy_loss``, ``token_logps``, ``logits_rows`` and
-        ``distill_loss``: batch metadata, embedding (NEFTune in training), the decoder layers and the final norm.
+        """The trunk shared by ``forward``, ``sequence_logps``, ``policy_loss``, ``token_logps``, ``logits_rows``,
+        ``distill_loss``, ``topk_logps_rows`` and ``distill_topk_loss``: batch metadata, embedding (NEFTune in training),
+        the decoder layers and the final norm.
         Returns (h [M, hidden], the shifted flat labels or None, cu_seqlens)."""
         dev = input_ids.device
         rope_cs = None

@@ -205,6 +205,80 @@ def lm_head_distill_loss(h, weight, teacher_logits, labels, inv_count, beta: flo
                                  float(temperature))
 
 
+# ----------------------------------------------------------------------------- LM head + offline distillation
+def teacher_topk(logits: torch.Tensor, k: int, temperature: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(int32 ids [M, k], fp32 log softmax(logits / temperature) at them [M, k]) of the k <= 256 largest logits of every
+    row, value descending and equal values by column ascending; the lse is the whole row's (csrc/distill_topk.hip;
+    ref.teacher_topk). ``logits`` [M, vocab] are only read."""
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    x = logits.reshape(-1, logits.shape[-1])
+    if _ext.use_hip(x):
+        ids, lps = _ext.ops().teacher_topk(x.contiguous(), int(k), float(temperature))
+        return ids, lps
+    ids, lps = ref.teacher_topk(x, int(k), temperature)
+    return ids, lps.float()
+
+
+def _kd_topk_rows(logits: torch.Tensor, ids: torch.Tensor, logps: torch.Tensor, labels: torch.Tensor,
+                  inv_count: torch.Tensor, write_grad: bool, temperature: float):
+    """Per-row forward KL against a teacher's cached top-k log-probabilities (csrc/distill_topk.hip kd_topk_fwd;
+    ref.distill_topk). Returns stats [5, M] fp32 = (loss, student lse, teacher mass kept, correct, agrees with
+    ids[:, 0]). If write_grad, logits is overwritten in place by d(sum(loss) * inv_count) / dlogits. The ids of a row
+    must be distinct and in [0, vocab): anything else is a caller error (the debug build asserts it)."""
+    if _ext.use_hip(logits):
+        return _ext.ops().kd_topk_fwd(logits, ids.contiguous(), logps.contiguous(), labels, inv_count, write_grad,
+                                      float(temperature))
+    loss, lse, mass, correct, agree = ref.distill_topk(logits, ids, logps, labels, temperature)
+    if write_grad:
+        logits.copy_(ref.distill_topk_grad(logits, ids, logps, labels, inv_count, temperature))
+    return torch.stack([loss, lse, mass, correct.to(loss.dtype), agree.to(loss.dtype)]).float()
+
+
+class LMHeadDistillTopKFn(Function):
+    """loss = sum_t sum_k p_tk (tlp_tk - log softmax(h_t W^T / tau)[id_tk]) * inv_count: LMHeadDistillFn with
+    _kd_topk_rows in place of _kd_rows. The cached tensors are read in the forward only and not saved."""
+
+    @staticmethod
+    def forward(ctx, h, weight, ids, logps, labels, inv_count, temperature):
+        h2d, logits, need_grad = _forward(ctx, h, weight)
+        stats = _kd_topk_rows(logits, ids, logps, labels.reshape(-1), inv_count, need_grad, temperature)
+        loss = (stats[0].sum() * inv_count.float()).reshape(())
+        _save(ctx, h, weight, need_grad, (h2d, logits), (stats,))
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        return (*_scalar_backward(ctx, dloss), None, None, None, None, None)
+
+
+def lm_head_distill_topk_loss(h, weight, ids, logps, labels, inv_count,
+                              temperature: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Offline distillation through the LM head: the forward KL(teacher || student) over the teacher's top-k support,
+    not renormalised, from cached ``ids`` int32 [M, k] and ``logps`` fp32 [M, k] (``teacher_topk`` /
+    ``lm_head_topk_logps`` of the same rows at the same ``temperature``). ``labels`` are already shifted (-100: the
+    row costs nothing and its cached values are never used). Returns (loss, stats [5, M])."""
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    M = h.numel() // h.shape[-1]
+    if ids.dim() >= 2 and ids.shape == logps.shape:  # [M, k], or a padded batch's [B, T, k]
+        ids, logps = ids.reshape(-1, ids.shape[-1]), logps.reshape(-1, ids.shape[-1])
+    if ids.dim() != 2 or ids.shape != logps.shape or ids.shape[0] != M or \
+            not 1 <= ids.shape[1] <= min(256, weight.shape[0]):
+        raise ValueError(f"ids / logps must both be [{M}, k] with 1 <= k <= min(256, vocab), got {tuple(ids.shape)} / "
+                         f"{tuple(logps.shape)}")
+    if ids.dtype != torch.int32 or logps.dtype != torch.float32:
+        raise ValueError(f"ids must be int32 and logps fp32, got {ids.dtype} / {logps.dtype}")
+    return LMHeadDistillTopKFn.apply(h, weight, ids, logps.detach(), labels, inv_count, float(temperature))
+
+
+def lm_head_topk_logps(h: torch.Tensor, weight: torch.Tensor, k: int,
+                       temperature: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The teacher's side of offline distillation, no autograd graph: the forward GEMM, then ``teacher_topk`` of its
+    logits. Returns (ids int32 [M, k], logps fp32 [M, k])."""
+    return teacher_topk(_logits(h.detach(), weight.detach())[1], k, temperature)
+
+
 # ----------------------------------------------------------------------------- sequence log-probs + DPO
 def seq_logp_sum(nll: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int) -> torch.Tensor:
     """logps[s] = -sum nll[cu[s] : cu[s + 1]], s < n_seqs (csrc/preference.hip; ref.seq_logp_sum)."""

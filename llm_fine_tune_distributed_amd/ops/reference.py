@@ -282,6 +282,63 @@ def generalized_jsd_grad(student_logits: torch.Tensor, teacher_logits: torch.Ten
     return g * rs[:, None]
 
 
+def teacher_topk(logits: torch.Tensor, k: int, temperature: float = 1.0):
+    """The k largest logits of every row as (int32 ids [M, k], log softmax(logits / temperature) at them [M, k], the
+    lse taken over the whole row): value descending, equal values by column ascending (a stable descending sort; -0 = +0).
+    Twin of csrc/distill_topk.hip teacher_topk; the log-probabilities are fp32 for logits below fp32, else the
+    logits' dtype."""
+    V = logits.shape[-1]
+    if not 1 <= int(k) <= min(256, V):
+        raise ValueError(f"k must be in 1 .. min(256, vocab={V}), got {k}")
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    x = logits.reshape(-1, V)
+    x = x if x.dtype in (torch.float32, torch.float64) else x.float()
+    vals, ids = torch.sort(x, dim=-1, descending=True, stable=True)
+    a = x / float(temperature)
+    lse = torch.logsumexp(a, -1, keepdim=True)
+    ids = ids[:, :int(k)]
+    return ids.to(torch.int32), a.gather(1, ids) - lse
+
+
+def _topk_terms(student_logits, ids, logps, temperature):
+    dt = student_logits.dtype if student_logits.dtype in (torch.float32, torch.float64) else torch.float32
+    a = student_logits.to(dt) / float(temperature)
+    lse = torch.logsumexp(a, -1)
+    return a - lse[:, None], lse, ids.to(torch.int64), logps.to(dt)
+
+
+def distill_topk(student_logits: torch.Tensor, ids: torch.Tensor, logps: torch.Tensor, labels: torch.Tensor,
+                 temperature: float = 1.0):
+    """Per-token forward KL of the student against a teacher truncated to its top-k support (twin of
+    csrc/distill_topk.hip kd_topk_fwd): with lp the student's log-softmax of logits / temperature, the cached
+    (id_k, tlp_k) of ``teacher_topk`` and p_k = e^tlp_k, L = sum_k p_k (tlp_k - lp[id_k]), not renormalised; at k = vocab
+    it is ``generalized_jsd`` at beta 0. A -100 row costs 0. The ids of a row must be distinct and in [0, vocab).
+    Returns (loss_per_token, student lse, the teacher mass kept m = sum_k p_k, student argmax == label, student argmax
+    == ids[:, 0]), the last two False on ignored rows."""
+    if not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    lp, lse, idx, tlp = _topk_terms(student_logits, ids, logps, temperature)
+    p = tlp.exp()
+    loss = (p * (tlp - lp.gather(1, idx))).sum(-1)
+    valid = labels != IGNORE_INDEX
+    loss = torch.where(valid, loss, torch.zeros_like(loss))
+    top = student_logits.argmax(-1)
+    return loss, lse, p.sum(-1), (top == labels) & valid, (top == idx[:, 0]) & valid
+
+
+def distill_topk_grad(student_logits: torch.Tensor, ids: torch.Tensor, logps: torch.Tensor, labels: torch.Tensor,
+                      scale: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+    """d(sum of ``distill_topk``'s per-token loss * scale) / d student_logits, zero on ignored rows:
+    (m softmax_j - sum_k [id_k = j] p_k) * scale / temperature."""
+    lp, _, idx, tlp = _topk_terms(student_logits, ids, logps, temperature)
+    p = tlp.exp()
+    g = p.sum(-1, keepdim=True) * lp.exp()
+    g = g.scatter_add(1, idx, -p)
+    rs = (labels != IGNORE_INDEX).to(g.dtype) * (scale.to(g.dtype) / float(temperature))
+    return g * rs[:, None]
+
+
 def embedding_noise_u(idx: torch.Tensor, seed: int) -> torch.Tensor:
     """The NEFTune uniform of element index ``idx`` (int64): (2 (hash_u32 >> 9) + 1 - 2^23) 2^-23 in fp32 — the odd
     integers of (-2^23, 2^23) scaled by 2^-23: exact, symmetric about 0, never 0 or +-1 (twin of

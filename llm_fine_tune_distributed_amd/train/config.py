@@ -348,6 +348,9 @@ class GKDConfig(SFTConfig):
     lmbda: float = 0.0         # share of on-policy (student-generated) batches; TRL's default is 0.5
     seq_kd: bool = False       # TRL: train on teacher-generated sequences
     teacher_model_name_or_path: Optional[str] = None  # preset name or local HF directory (or GKDTrainer(teacher_model=))
+    # offline distillation: cache the teacher's top-k token log-probabilities once (output_dir/teacher_topk-<fp>.pt) and
+    # train from the cache, without the teacher's forward in the step; 1..256, forward KL only (beta=0). None: online
+    teacher_topk: Optional[int] = None
 
     def __post_init__(self):
         self.validate_objective()
@@ -376,6 +379,15 @@ class GKDConfig(SFTConfig):
             raise ValueError(f"GKDConfig: beta must be in [0, 1], got {self.beta}")
         if not float(self.temperature) > 0:
             raise ValueError(f"GKDConfig: temperature must be > 0, got {self.temperature}")
+        if self.teacher_topk is not None:
+            k = self.teacher_topk
+            if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 256:
+                raise ValueError(f"GKDConfig: teacher_topk must be None or an integer in 1..256, got {k!r}")
+            if float(self.beta) != 0.0:
+                raise ValueError(f"GKDConfig: teacher_topk={k} with beta={self.beta}: a teacher truncated to its top-k "
+                                 "tokens defines only the forward KL (the reverse KL and the JSD mixture need the "
+                                 "teacher's probability of every token the student gives mass to); set beta=0 (the "
+                                 "default is 0.5)")
 
 
 GKDConfig.__init__ = _tolerant_init(GKDConfig.__init__)
