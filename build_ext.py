@@ -31,6 +31,11 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
+# Extra hipcc flags per source file. attention_d64.hip is compiled without the packed fp32 VALU instructions
+# (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): its accumulator rescales and softmax arithmetic stay scalar fp32 ops.
+EXTRA_HIP_FLAGS = {"attention_d64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def torch_paths():
     import torch
     tdir = os.path.dirname(torch.__file__)
@@ -72,7 +77,8 @@ def main(argv=None) -> str:
         if not args.force and newer(obj, [src, __file__] + headers):
             continue
         if src.endswith(".hip"):
-            cmd = [os.path.join(ROCM, "bin", "hipcc"), "-c", src, "-o", obj] + hip_flags
+            cmd = ([os.path.join(ROCM, "bin", "hipcc"), "-c", src, "-o", obj] + hip_flags
+                   + EXTRA_HIP_FLAGS.get(os.path.basename(src), []))
         else:
             cmd = ["g++", "-c", src, "-o", obj] + cxx_flags
         jobs.append((src, cmd))

@@ -21,6 +21,7 @@
 //   {4g+i} from t0 and {16+4g+i} from t1; we use that order as the k permutation
 //   p(8g+j) = j<4 ? 4g+j : 16+4g+(j-4) on BOTH operands of the next MFMA.
 // The 32x32x16 lane maps are at fwd32 below.
+#include "attention_d64.h"
 #include "common.h"
 #include "gemm_prims.h"
 #include "qkv_rows.h"
@@ -925,11 +926,14 @@ static void launch_dkdv(const u16* qkv, const u16* dout, const float* lse, const
 
 }  // namespace attn
 
-static void check_attn_args(const at::Tensor& qkv, const at::Tensor& cu, int64_t nq, int64_t nkv, int64_t hd) {
+static void check_attn_args(const at::Tensor& qkv, const at::Tensor& cu, int64_t nq, int64_t nkv, int64_t hd,
+                            int64_t window) {
   SFT_CHECK_CUDA(qkv);
   SFT_CHECK_BF16(qkv);
   SFT_CHECK_CONTIG(qkv);
-  SFT_CHECK(hd == attn::D, "flash attention kernel is built for head_dim 128, got ", hd);
+  SFT_CHECK(hd == attn::D || hd == attn64::D, "flash attention kernels are built for head_dim 128 and 64, got ", hd);
+  SFT_CHECK(hd == attn::D || window <= 0, "flash attention: no sliding window at head_dim 64 (window ", window,
+            "): the windowed kernels are built for head_dim 128");
   SFT_CHECK(nq % nkv == 0, "nq must be a multiple of nkv");
   SFT_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * hd, "qkv must be [M, (nq+2nkv)*hd]");
   SFT_CHECK(cu.scalar_type() == at::kInt && cu.is_cuda() && cu.dim() == 1 && cu.numel() >= 2, "cu_seqlens int32");
@@ -955,7 +959,7 @@ static long attn_ds_budget() {
 std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Tensor& cu, int64_t max_seqlen,
                                              int64_t nq, int64_t nkv, int64_t hd, double scale, bool causal,
                                              int64_t window) {
-  check_attn_args(qkv, cu, nq, nkv, hd);
+  check_attn_args(qkv, cu, nq, nkv, hd, window);
   const int win = attn_window(window, causal, max_seqlen);
   const int total = qkv.size(0);
   const int nseq = cu.numel() - 1;
@@ -969,6 +973,10 @@ std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Te
   float* lp = lse.data_ptr<float>();
   const int* cp = cu_c.data_ptr<int>();
   const int ca = causal ? 1 : 0;
+  if (hd == attn64::D) {
+    attn64::launch_fwd(q, o, lp, cp, nq, nkv, total, nseq, max_seqlen, sl2, ca, cur_stream());
+    return {out, lse};
+  }
   SFT_TRACE("attn.fwd32");
   const int rep = nq / nkv, hw = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1, span = 32 * (4 / hw);
   dim3 g(nq / hw, nseq, (max_seqlen + span - 1) / span);
@@ -998,7 +1006,7 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
                                  const float* rsin, bool& rope_done, const c10::optional<at::Tensor>& delta_in,
                                  int64_t window) {
   rope_done = false;
-  check_attn_args(qkv, cu, nq, nkv, hd);
+  check_attn_args(qkv, cu, nq, nkv, hd, window);
   const int win = attn_window(window, causal, max_seqlen);
   SFT_CHECK_CONTIG(dout);
   SFT_CHECK_CONTIG(out);
@@ -1013,6 +1021,10 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
     SFT_CHECK(delta.scalar_type() == at::kFloat && delta.is_contiguous() && delta.dim() == 2 && delta.size(0) == nq &&
                   delta.size(1) == total && delta.device() == qkv.device(),
               "flash_bwd: delta must be contiguous fp32 [n_q, total]");
+  } else if (hd == attn64::D) {
+    delta = at::empty({nq, total}, qkv.options().dtype(at::kFloat));
+    attn64::launch_delta((const u16*)dout.data_ptr(), (const u16*)out.data_ptr(), delta.data_ptr<float>(), total, nq,
+                         cur_stream());
   } else {
     SFT_TRACE("attn.delta_kernel");
     delta = at::empty({nq, total}, qkv.options().dtype(at::kFloat));
@@ -1026,6 +1038,12 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
   auto cu_c = cu.contiguous();
   const u16* q = (const u16*)qkv.data_ptr();
   const u16* dO = (const u16*)dout.data_ptr();
+  if (hd == attn64::D) {  // (rope_done stays false: flash_bwd_rope runs the rope kernel on dqkv)
+    attn64::launch_bwd(q, dO, lse.data_ptr<float>(), delta.data_ptr<float>(), cu_c.data_ptr<int>(),
+                       (u16*)dqkv.data_ptr(), nq, nkv, total, nseq, max_seqlen, sl2, (float)scale, causal ? 1 : 0,
+                       cur_stream());
+    return dqkv;
+  }
   const long lp = (max_seqlen + 127) / 128 * 128;
   const long ds_bytes = (long)nseq * nq * lp * lp * 2;
   if (ds_bytes <= attn_ds_budget()) {

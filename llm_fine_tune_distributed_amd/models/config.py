@@ -317,6 +317,31 @@ def mistral_7b() -> ModelConfig:
     )
 
 
+# The two head_dim-64 shapes below are written from memory of the published config.json files too (no copy of them was
+# at hand): a real checkpoint directory's own config.json always wins (get_config on the directory).
+def llama3_2_1b() -> ModelConfig:
+    """meta-llama/Llama-3.2-1B shape: 32 q / 8 kv heads of 64, Llama-3's vocabulary, tied embeddings, llama3 RoPE
+    scaling (csrc/attention_d64.hip)."""
+    return ModelConfig(
+        model_type="llama", vocab_size=128256, hidden_size=2048, intermediate_size=8192, num_hidden_layers=16,
+        num_attention_heads=32, num_key_value_heads=8, head_dim=64, rope_theta=500000.0,
+        rope_scaling={"rope_type": "llama3", "factor": 32.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                      "original_max_position_embeddings": 8192},
+        max_position_embeddings=131072, tie_word_embeddings=True, rms_norm_eps=1e-5, eos_token_id=128001,
+        pad_token_id=None,
+    )
+
+
+def smollm2_1_7b() -> ModelConfig:
+    """HuggingFaceTB/SmolLM2-1.7B shape: Llama's architecture, 32 q / 32 kv heads of 64 (MHA), tied embeddings."""
+    return ModelConfig(
+        model_type="llama", vocab_size=49152, hidden_size=2048, intermediate_size=8192, num_hidden_layers=24,
+        num_attention_heads=32, num_key_value_heads=32, head_dim=64, rope_theta=130000.0,
+        max_position_embeddings=8192, tie_word_embeddings=True, rms_norm_eps=1e-5, bos_token_id=0, eos_token_id=0,
+        pad_token_id=None,
+    )
+
+
 def tiny(model_type: str = "smollm3", **kw) -> ModelConfig:
     """Small config with the same structure (GQA, NoPE interval, tied head) for tests."""
     base = dict(
@@ -365,9 +390,24 @@ PRESETS = {
 }
 
 
+# The head_dim-64 families (csrc/attention_d64.hip). A table of their own: PRESETS is exactly the set of names whose
+# config.json digests tests/golden/preset_config_sha256.json pins (tests/test_reward_cpu.py compares the two sets).
+PRESETS_D64 = {
+    "llama3.2-1b": llama3_2_1b,
+    "meta-llama/Llama-3.2-1B": llama3_2_1b,
+    "smollm2-1.7b": smollm2_1_7b,
+    "HuggingFaceTB/SmolLM2-1.7B": smollm2_1_7b,
+    # the tiny-gpu shape with 4 q / 2 kv heads of 64 (GPU tests)
+    "tiny-gpu-d64": lambda: tiny(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64,
+                                 intermediate_size=512, vocab_size=1024, num_hidden_layers=3),
+}
+
+
 def get_config(name_or_path: str) -> ModelConfig:
     if name_or_path in PRESETS:
         return PRESETS[name_or_path]()
+    if name_or_path in PRESETS_D64:
+        return PRESETS_D64[name_or_path]()
     if os.path.isdir(name_or_path) and os.path.exists(os.path.join(name_or_path, "config.json")):
         return ModelConfig.from_pretrained(name_or_path)
-    raise ValueError(f"unknown model {name_or_path!r}; presets: {sorted(PRESETS)}")
+    raise ValueError(f"unknown model {name_or_path!r}; presets: {sorted({**PRESETS, **PRESETS_D64})}")

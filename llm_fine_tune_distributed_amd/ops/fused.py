@@ -338,7 +338,8 @@ class AttnLink:
 
     def __init__(self):
         # written by the attention node's forward (the HIP flash forward ran, head_dim 128); read by attn_out_linear and
-        # o_proj's backward (AttnOutLinearFn): the delta hand-off is allowed
+        # o_proj's backward (AttnOutLinearFn): the delta hand-off is allowed. At head_dim 64 it stays off: o_proj is a
+        # plain linear and the attention backward runs its own delta kernel (csrc/attention_d64.hip)
         self.delta_ok = False
         # written by the qkv node's forward (its backward will run); read by o_proj's backward before it defers o_job
         self.qkv_takes_o_wgrad = False
@@ -1071,7 +1072,8 @@ class QKVRopeFn(Function):
 
 def _rope_epilogue_ok(x2d, weight, cos, sin, head_dim) -> bool:
     """What the RoPE epilogue of gemm_tn_rope takes, on top of its caller's own GEMM shape rule (_tn_ok, or the LoRA
-    wide guard): head_dim 128, whole 256 x 256 tiles, and contiguous fp32 cos / sin tables [M, 64]."""
+    wide guard): head_dim 128, whole 256 x 256 tiles, and contiguous fp32 cos / sin tables [M, 64]. A head_dim-64
+    model takes the plain projection, the rope kernel and flash_attention (the head_dim-64 kernels) instead."""
     return (head_dim == 128 and _ext.use_hip(x2d) and x2d.shape[0] % 256 == 0 and weight.shape[0] % 256 == 0
             and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
             and cos.shape == (x2d.shape[0], 64))
@@ -1241,6 +1243,9 @@ def qkv_bias_rope_(qkv, bias, cos, sin, n_q, n_kv, head_dim):
 
 # ----------------------------------------------------------------------------- attention
 class FlashAttnFn(Function):
+    """Varlen GQA flash attention on the packed qkv. On the HIP path head_dim is 128 (csrc/attention.hip) or 64
+    (csrc/attention_d64.hip: no sliding window, no delta hand-off from o_proj); any other head_dim raises there."""
+
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale, causal, link=None, window=0):
         ctx.dims = (max_seqlen, n_q, n_kv, head_dim, scale, causal, window)

@@ -34,6 +34,30 @@ def attn_ok():
                 assert len(slots) == 32, ("attn tr", R, dt)
 
 
+def attn_d64_ok():
+    # csrc/attention_d64.hip: a 64-row tile of 128-B head rows as 32 image rows of 256 B (tile row r in chunks 0..7,
+    # r + 32 in chunks 8..15) under attn_swz, read by the 32x32x16 kernels (hi = lane >> 5, c = lane & 31).
+    # 16-B row reads: tile row 32 b + c, chunk 2 s + hi  ->  image row c, chunk 8 b + 2 s + hi
+    for b in range(2):
+        for s in range(4):
+            for grp in B128_GROUPS:
+                slots = {attn_swz(l & 31, 8 * b + 2 * s + (l >> 5)) for l in grp}
+                assert len(slots) == 16, ("attn d64 row", b, s)
+    # transposed reads: a = lane >> 4, q = (lane & 15) >> 2, p = lane & 3: tile rows 32 b + 16 sub + 8 part + 4 hi + q,
+    # columns 32 db + 16 (a & 1) + 4 p ..  ->  image row 16 sub + 8 part + 4 hi + q, chunk 8 b + 4 db + 2 (a & 1) + (p >> 1)
+    for b in range(2):
+        for sub in range(2):
+            for part in range(2):
+                for db in range(2):
+                    for half in (range(0, 32), range(32, 64)):
+                        slots = set()
+                        for l in half:
+                            hi, a, q, p = l >> 5, l >> 4, (l & 15) >> 2, l & 3
+                            row = 16 * sub + 8 * part + 4 * hi + q
+                            slots.add(2 * attn_swz(row, 8 * b + 4 * db + 2 * (a & 1) + (p >> 1)) + (p & 1))
+                        assert len(slots) == 32, ("attn d64 tr", b, sub, part, db)
+
+
 def tn_ok():
     # csrc/gemm_dgrad.hip dY image (swz64): 64-B rows, chunk ^ S((row >> 2) & 3);
     # csrc/gemm_tn.hip and gemm_dgrad.hip BK64 (swz128): 128-B rows, chunk ^ ((row >> 1) & 7)
@@ -49,5 +73,6 @@ def tn_ok():
 
 if __name__ == "__main__":
     attn_ok()
+    attn_d64_ok()
     tn_ok()
     print("all LDS swizzles conflict-free on the MI355X lane groups")
