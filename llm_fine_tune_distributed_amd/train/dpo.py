@@ -11,7 +11,6 @@ A resume loads that file and fails if it is missing: the resumed weights are not
 """
 from __future__ import annotations
 
-import hashlib
 import os
 from typing import Any, Dict, List, Optional
 
@@ -21,55 +20,32 @@ from .. import ops
 from ..data.collator import DataLoader, DistributedBatchSampler
 from ..data.dataset import TokenizedDataset
 from ..data.preference import PreferenceCollator, cached_tokenize_preferences
-from ..models import CausalLM, build_model, get_config
+from ..models import CausalLM
 from ..parallel.process_group import all_reduce_sum_, barrier
-from . import checkpoint as ckpt
 from .config import DPOConfig
+from .frozen import dataset_fingerprint, resolve_model, resolve_resume, save_on_main, to_device
 from .trainer import SFTTrainer, TrainOutput
 
 
-class DPOTrainer(SFTTrainer):
-    # loss, reward_chosen, reward_rejected, accurate pairs, margin, logp_chosen, logp_rejected, pairs
-    _acc_size = 8
+class PairDataMixin:
+    """The data side of a trainer on preference pairs (``DPOTrainer``, ``RewardTrainer``), in front of ``SFTTrainer``:
+    the datasets hold 2N sequences, the loaders sample pair indices, a ``PreferenceCollator`` per set builds the
+    batches."""
 
-    def __init__(self, model=None, args: Optional[DPOConfig] = None, train_dataset=None, eval_dataset=None,
-                 ref_model=None, **kw):
-        args = args or DPOConfig()
-        if not isinstance(args, DPOConfig):
-            raise TypeError("DPOTrainer expects a DPOConfig")
-        if int(getattr(args, "context_parallel_size", 1) or 1) > 1:
-            raise NotImplementedError("DPOTrainer under context parallelism: per-sequence log-probabilities are not "
-                                      "reduced across a context-parallel group")
-        if kw.get("data_collator") is not None:
-            raise ValueError("DPOTrainer builds its own PreferenceCollator")
-        self._ref_model = ref_model
-        self._ref_ready = False
-        super().__init__(model, args, train_dataset, eval_dataset, **kw)
+    def _init_pair_data(self, pad_multiple: Optional[int], need_loss_start: bool = False) -> None:
+        """After ``SFTTrainer.__init__``: checks the prepared sets and builds the two collators."""
         for ds in (self.train_dataset, self.eval_dataset):
-            if ds is not None and (len(ds) % 2 or ds.loss_start is None):
-                raise ValueError("a preference dataset holds 2N sequences (chosen at 2i, rejected at 2i + 1) with "
-                                 "loss_start = the prompt length")
-        pad_mult = args.pad_to_multiple_of
-        if pad_mult is None and self.dist.device.type == "cuda":
-            pad_mult = 256
+            if ds is not None and (len(ds) % 2 or (need_loss_start and ds.loss_start is None)):
+                raise ValueError("a preference dataset holds 2N sequences (chosen at 2i, rejected at 2i + 1)"
+                                 + (" with loss_start = the prompt length" if need_loss_start else ""))
+        if pad_multiple is None and self.dist.device.type == "cuda":
+            pad_multiple = 256
         self.packed = True
-        self.collator = PreferenceCollator(self._pad_id, pad_mult)       # carries the train set's ref_logps
-        self.eval_collator = PreferenceCollator(self._pad_id, pad_mult)  # the eval set's
+        self.collator = PreferenceCollator(self._pad_id, pad_multiple)       # carries the train set's per-pair data
+        self.eval_collator = PreferenceCollator(self._pad_id, pad_multiple)  # the eval set's
 
-    # ------------------------------------------------------------------ data
     def _sparse_cap(self) -> int:
         return 0  # (a batch holds 2 x batch-size sequences: every rank measures its pass)
-
-    def _prepare(self, ds, limit):
-        if ds is None or isinstance(ds, TokenizedDataset):
-            return ds
-        rows = list(ds) if not isinstance(ds, list) else ds
-        if limit:
-            rows = rows[:limit]
-        return cached_tokenize_preferences(rows, self.tokenizer, self._cache_dir(), is_main=self.dist.is_main,
-                                           barrier=barrier if self.dist.world_size > 1 else None,
-                                           max_length=self.args.max_length,
-                                           max_prompt_length=self.args.max_prompt_length)
 
     def _loader(self, ds, collator, batch_size, **sampler_kw) -> DataLoader:
         a = self.args
@@ -87,22 +63,45 @@ class DPOTrainer(SFTTrainer):
 
     def _merge_micro(self, micro: List[Dict]) -> List[Dict]:
         # GA micro-batches stay separate passes: a merged varlen batch would interleave each micro-batch's pad segment
-        # with the sequences, and sequence_logps takes the first n_seqs segments
+        # with the sequences, and sequence_logps / sequence_scores take the first n_seqs segments
         return micro
 
-    # ------------------------------------------------------------------ reference log-probs
-    def _ref_fingerprint(self) -> str:
-        h = hashlib.sha256()
-        for ds in (self.train_dataset, self.eval_dataset):
-            if ds is None:
-                h.update(b"none")
-                continue
-            for t in (ds.tokens, ds.offsets, ds.loss_start):
-                h.update(t.contiguous().cpu().numpy().tobytes())
-        return h.hexdigest()[:16]
 
+class DPOTrainer(PairDataMixin, SFTTrainer):
+    # loss, reward_chosen, reward_rejected, accurate pairs, margin, logp_chosen, logp_rejected, pairs
+    _acc_size = 8
+
+    def __init__(self, model=None, args: Optional[DPOConfig] = None, train_dataset=None, eval_dataset=None,
+                 ref_model=None, **kw):
+        args = args or DPOConfig()
+        if not isinstance(args, DPOConfig):
+            raise TypeError("DPOTrainer expects a DPOConfig")
+        if int(getattr(args, "context_parallel_size", 1) or 1) > 1:
+            raise NotImplementedError("DPOTrainer under context parallelism: per-sequence log-probabilities are not "
+                                      "reduced across a context-parallel group")
+        if kw.get("data_collator") is not None:
+            raise ValueError("DPOTrainer builds its own PreferenceCollator")
+        self._ref_model = ref_model
+        self._ref_ready = False
+        super().__init__(model, args, train_dataset, eval_dataset, **kw)
+        self._init_pair_data(args.pad_to_multiple_of, need_loss_start=True)  # (the collators carry ref_logps)
+
+    # ------------------------------------------------------------------ data
+    def _prepare(self, ds, limit):
+        if ds is None or isinstance(ds, TokenizedDataset):
+            return ds
+        rows = list(ds) if not isinstance(ds, list) else ds
+        if limit:
+            rows = rows[:limit]
+        return cached_tokenize_preferences(rows, self.tokenizer, self._cache_dir(), is_main=self.dist.is_main,
+                                           barrier=barrier if self.dist.world_size > 1 else None,
+                                           max_length=self.args.max_length,
+                                           max_prompt_length=self.args.max_prompt_length)
+
+    # ------------------------------------------------------------------ reference log-probs
     def ref_logps_path(self) -> str:
-        return os.path.join(self.args.output_dir, f"ref_logps-{self._ref_fingerprint()}.pt")
+        fp = dataset_fingerprint((self.train_dataset, self.eval_dataset))
+        return os.path.join(self.args.output_dir, f"ref_logps-{fp}.pt")
 
     @staticmethod
     def _seq_inputs(b: Dict) -> Dict:
@@ -138,27 +137,15 @@ class DPOTrainer(SFTTrainer):
             d = torch.load(path, weights_only=True)
         else:
             self.optimizer.synchronize()
+            # (not hold_frozen: the reference may be the policy itself, and goes back to the mode it was in)
             ref = self._ref_model if self._ref_model is not None else self.model
-            if isinstance(ref, str):
-                dev = self.dist.device
-                if os.path.isdir(ref) and any(f.endswith(".safetensors") for f in os.listdir(ref)):
-                    ref = ckpt.from_pretrained(ref, device=dev, dtype=torch.bfloat16)
-                else:
-                    ref = build_model(get_config(ref), device=dev, dtype=torch.bfloat16)
-            elif next(ref.parameters()).device != self.dist.device:
-                ref.to(self.dist.device)
-                ref.inv_freq = ref.inv_freq.to(self.dist.device)
+            ref = to_device(resolve_model(ref, self.dist.device), self.dist.device)
             was_training = ref.training
             ref.eval()
             d = {"train": self._compute_ref(ref, self.train_dataset), "eval": self._compute_ref(ref, self.eval_dataset)}
             ref.train(was_training)
             self._ref_model = ref = None  # evaluated once, then released
-            if self.dist.is_main:
-                os.makedirs(self.args.output_dir, exist_ok=True)
-                tmp = f"{path}.tmp{os.getpid()}"
-                torch.save(d, tmp)
-                os.replace(tmp, path)
-            barrier()
+            save_on_main(d, path, self.dist.is_main)
         if self.train_dataset is not None and (d.get("train") is None or d["train"].numel() != len(self.train_dataset)):
             raise ValueError(f"{path} does not match the training set")
         self.collator.ref_logps = d.get("train")
@@ -212,8 +199,5 @@ class DPOTrainer(SFTTrainer):
         return super().evaluate(None, metric_key_prefix)
 
     def train(self, resume_from_checkpoint: Optional[str] = None) -> TrainOutput:
-        resume = resume_from_checkpoint or self.args.resume_from_checkpoint
-        if resume is True or resume == "auto":
-            resume = ckpt.latest_checkpoint(self.args.output_dir)
-        self._ensure_ref_logps(resume=bool(resume))
+        self._ensure_ref_logps(resume=bool(resolve_resume(self.args, resume_from_checkpoint)))
         return super().train(resume_from_checkpoint)

@@ -20,18 +20,16 @@ With a matching file present no teacher is needed at all; a resume needs the fil
 """
 from __future__ import annotations
 
-import hashlib
 import os
 from typing import Any, Dict, List, Optional
 
 import torch
 
-from ..data.collator import DataLoader, DistillTopKCollator, SFTCollator
+from ..data.collator import DistillTopKCollator, SFTCollator
 from ..data.dataset import TokenizedDataset
-from ..models import CausalLM, build_model, get_config
-from ..parallel.process_group import all_reduce_sum_, barrier
-from . import checkpoint as ckpt
+from ..parallel.process_group import all_reduce_sum_
 from .config import GKDConfig
+from .frozen import dataset_fingerprint, hold_frozen, resolve_model, resolve_resume, save_on_main
 from .trainer import SFTTrainer, TrainOutput
 
 
@@ -56,7 +54,7 @@ class GKDTrainer(SFTTrainer):
         if self.topk is not None and kw.get("data_collator") is not None:
             raise ValueError("GKDTrainer with teacher_topk builds its own DistillTopKCollator")
         super().__init__(model, args, train_dataset, eval_dataset, **kw)
-        self._topk_ready = False
+        self._topk_ready, self._topk_fp = False, None
         if self.topk is not None:
             self._acc_size = 5  # ... and the teacher mass kept, summed over the valid rows
             c = self.collator
@@ -67,54 +65,25 @@ class GKDTrainer(SFTTrainer):
                 teacher_model = None  # the cache stands in for the teacher
             elif teacher_model is None:
                 raise no_teacher
-        self.teacher = self._load_teacher(teacher_model) if teacher_model is not None else None
-        if self.teacher is not None:
+        self.teacher = None
+        if teacher_model is not None:
+            dev = self.dist.device
+            self.teacher = hold_frozen(resolve_model(teacher_model, dev), dev, trained=self.model, what="teacher",
+                                       cast_bf16=True)
             vs, vt = self.model.config.vocab_size, self.teacher.config.vocab_size
             if vs != vt:
                 raise ValueError(f"the teacher's vocab_size ({vt}) differs from the student's ({vs}): distillation "
                                  "compares the two token distributions column by column, so both models need one "
                                  "tokenizer")
 
-    def _load_teacher(self, teacher) -> CausalLM:
-        dev = self.dist.device
-        if isinstance(teacher, str):
-            if os.path.isdir(teacher) and any(f.endswith(".safetensors") for f in os.listdir(teacher)):
-                teacher = ckpt.from_pretrained(teacher, device=dev, dtype=torch.bfloat16)
-            else:
-                teacher = build_model(get_config(teacher), device=dev, dtype=torch.bfloat16)
-        if not isinstance(teacher, CausalLM):
-            raise TypeError("teacher_model must be a preset name, a local HF directory or a CausalLM")
-        if teacher is self.model:
-            raise ValueError("the teacher must not be the student object: it is frozen and never updated")
-        if next(teacher.parameters()).device != dev:
-            teacher.to(dev)
-            teacher.inv_freq = teacher.inv_freq.to(dev)
-        for p in teacher.parameters():  # (the parameters only: inv_freq stays fp32)
-            if p.dtype != torch.bfloat16:
-                p.data = p.data.to(torch.bfloat16)
-        teacher.eval()
-        teacher.requires_grad_(False)
-        return teacher
-
     # ------------------------------------------------------------------ the teacher's cached top-k log-probabilities
-    def _topk_fingerprint(self) -> str:
-        """DPOTrainer._ref_fingerprint's data hash, plus what the cached values depend on besides the teacher. Hashed
-        once: the datasets, k and the temperature are fixed when the trainer is built (evaluate() takes no other set)."""
-        if getattr(self, "_topk_fp", None) is not None:
-            return self._topk_fp
-        h = hashlib.sha256()
-        for ds in (self.train_dataset, self.eval_dataset):
-            if ds is None:
-                h.update(b"none")
-                continue
-            for t in (ds.tokens, ds.offsets, ds.loss_start):
-                h.update(b"none" if t is None else t.contiguous().cpu().numpy().tobytes())
-        h.update(repr((self.topk, float(self.args.temperature), int(self.model.config.vocab_size))).encode())
-        self._topk_fp = h.hexdigest()[:16]
-        return self._topk_fp
-
     def teacher_topk_path(self) -> str:
-        return os.path.join(self.args.output_dir, f"teacher_topk-{self._topk_fingerprint()}.pt")
+        """(Hashed once: the datasets, k and the temperature are fixed when the trainer is built; evaluate() takes no
+        other set.)"""
+        if self._topk_fp is None:
+            self._topk_fp = dataset_fingerprint((self.train_dataset, self.eval_dataset), extra=(
+                self.topk, float(self.args.temperature), int(self.model.config.vocab_size)))
+        return os.path.join(self.args.output_dir, f"teacher_topk-{self._topk_fp}.pt")
 
     def _topk_meta(self) -> Dict[str, Any]:
         return {"k": self.topk, "temperature": float(self.args.temperature),
@@ -169,12 +138,7 @@ class GKDTrainer(SFTTrainer):
                 r = self._compute_topk(ds)
                 if r is not None:
                     d[f"{name}_ids"], d[f"{name}_logps"] = r
-            if self.dist.is_main:
-                os.makedirs(self.args.output_dir, exist_ok=True)
-                tmp = f"{path}.tmp{os.getpid()}"
-                torch.save(d, tmp)
-                os.replace(tmp, path)
-            barrier()
+            save_on_main(d, path, self.dist.is_main)
         if d.get("meta") != self._topk_meta():
             raise ValueError(f"{path} was written for {d.get('meta')}, this run asks for {self._topk_meta()}")
         for name, ds, coll in (("train", self.train_dataset, self.collator), ("eval", self.eval_dataset,
@@ -197,15 +161,6 @@ class GKDTrainer(SFTTrainer):
         if self.topk is None:
             raise ValueError("precompute_teacher_topk needs args.teacher_topk")
         self._ensure_teacher_topk()
-
-    def get_eval_dataloader(self) -> DataLoader:
-        if self.topk is None:
-            return super().get_eval_dataloader()
-        train_collator, self.collator = self.collator, self.eval_collator  # the inherited loader, the eval set's rows
-        try:
-            return super().get_eval_dataloader()
-        finally:
-            self.collator = train_collator
 
     def _merge_micro(self, micro: List[Dict]) -> List[Dict]:
         out = super()._merge_micro(micro)
@@ -231,10 +186,7 @@ class GKDTrainer(SFTTrainer):
 
     def train(self, resume_from_checkpoint: Optional[str] = None) -> TrainOutput:
         if self.topk is not None:
-            resume = resume_from_checkpoint or self.args.resume_from_checkpoint
-            if resume is True or resume == "auto":
-                resume = ckpt.latest_checkpoint(self.args.output_dir)
-            self._ensure_teacher_topk(resume=bool(resume))
+            self._ensure_teacher_topk(resume=bool(resolve_resume(self.args, resume_from_checkpoint)))
         return super().train(resume_from_checkpoint)
 
     # ------------------------------------------------------------------ objective

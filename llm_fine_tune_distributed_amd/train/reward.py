@@ -13,20 +13,18 @@ travels on the collator indexed by pair. An already tokenised ``TokenizedDataset
 """
 from __future__ import annotations
 
-import dataclasses
-import os
 from typing import Any, Dict, List, Optional
 
 import torch
 
 from .. import ops
-from ..data.collator import DataLoader, DistributedBatchSampler
 from ..data.dataset import TokenizedDataset
-from ..data.preference import PreferenceCollator, cached_tokenize_preferences, preference_margins
-from ..models import CausalLM, build_model, get_config
+from ..data.preference import cached_tokenize_preferences, preference_margins
+from ..models import CausalLM
 from ..parallel.process_group import barrier, setup_distributed
-from . import checkpoint as ckpt
 from .config import RewardConfig
+from .dpo import PairDataMixin
+from .frozen import resolve_model
 from .trainer import SFTTrainer
 
 # the accumulator after the loss: pairs with r_c > r_r, sum of r_c - r_r, sum of all rewards, pairs
@@ -37,19 +35,14 @@ def load_reward_model(model, device, seed: int = 0) -> CausalLM:
     """``model`` as a reward model on ``device``: a preset name (built with ``num_labels=1``), a local HF directory (a
     ``...ForSequenceClassification`` one as saved; a causal-LM one keeps its trunk, drops ``lm_head.weight`` and gets a
     fresh head from ``seed``), or a model object that already has a score head."""
-    if isinstance(model, str):
-        if os.path.isdir(model) and any(f.endswith(".safetensors") for f in os.listdir(model)):
-            model = ckpt.from_pretrained(model, device=device, dtype=torch.bfloat16, num_labels=1, seed=seed)
-        else:
-            cfg = dataclasses.replace(get_config(model), num_labels=1)
-            model = build_model(cfg, device=device, dtype=torch.bfloat16, seed=seed)
+    model = resolve_model(model, device, seed=seed, num_labels=1)
     if not isinstance(model, CausalLM) or model.score is None:
         raise TypeError("a reward model is expected: a preset name, a local HF directory, or a model built with "
                         f"num_labels=1 (got {type(model).__name__} without a score head)")
     return model
 
 
-class RewardTrainer(SFTTrainer):
+class RewardTrainer(PairDataMixin, SFTTrainer):
     _acc_size = 5
 
     def __init__(self, model=None, args: Optional[RewardConfig] = None, train_dataset=None, eval_dataset=None, **kw):
@@ -67,22 +60,12 @@ class RewardTrainer(SFTTrainer):
         self._margins: Dict[str, Optional[torch.Tensor]] = {}
         self._prepare_slot = "train"
         super().__init__(model, args, train_dataset, eval_dataset, **kw)
-        for ds in (self.train_dataset, self.eval_dataset):
-            if ds is not None and len(ds) % 2:
-                raise ValueError("a preference dataset holds 2N sequences (chosen at 2i, rejected at 2i + 1)")
-        pad_mult = args.pad_to_multiple_of
-        if pad_mult is None and self.dist.device.type == "cuda":
-            pad_mult = 256
-        self.packed = True
-        self.collator = PreferenceCollator(self._pad_id, pad_mult, margins=self._margins.get("train"))
-        self.eval_collator = PreferenceCollator(self._pad_id, pad_mult, margins=self._margins.get("eval"))
+        self._init_pair_data(args.pad_to_multiple_of)
+        self.collator.margins, self.eval_collator.margins = self._margins.get("train"), self._margins.get("eval")
         self._center = float(args.center_rewards_coefficient or 0.0)
         self._extremes = {"train": None, "eval": None}  # running (max reward, max of -reward) of a log window / an eval
 
     # ------------------------------------------------------------------ data
-    def _sparse_cap(self) -> int:
-        return 0  # (a batch holds 2 x batch-size sequences: every rank measures its pass)
-
     def _prepare(self, ds, limit):
         # (called for the train set, then the eval set, by the base constructor; by evaluate() for a new eval set)
         slot, self._prepare_slot = self._prepare_slot, "eval"
@@ -96,25 +79,6 @@ class RewardTrainer(SFTTrainer):
         return cached_tokenize_preferences(rows, self.tokenizer, self._cache_dir(), is_main=self.dist.is_main,
                                            barrier=barrier if self.dist.world_size > 1 else None,
                                            max_length=self.args.max_length, max_prompt_length=None)
-
-    def _loader(self, ds, collator, batch_size, **sampler_kw) -> DataLoader:
-        a = self.args
-        s = DistributedBatchSampler(len(ds) // 2, batch_size, self.dp_size, self.dp_rank,
-                                    drop_last=a.dataloader_drop_last, **sampler_kw)
-        return DataLoader(ds, collator, s, self.dist.device, a.dataloader_pin_memory, a.prefetch_batches)
-
-    def get_train_dataloader(self) -> DataLoader:
-        a = self.args
-        return self._loader(self.train_dataset, self.collator, a.per_device_train_batch_size, shuffle=True,
-                            seed=a.data_seed or a.seed)
-
-    def get_eval_dataloader(self) -> DataLoader:
-        return self._loader(self.eval_dataset, self.eval_collator, self.args.per_device_eval_batch_size, shuffle=False)
-
-    def _merge_micro(self, micro: List[Dict]) -> List[Dict]:
-        # GA micro-batches stay separate passes: a merged varlen batch would interleave each micro-batch's pad segment
-        # with the sequences, and sequence_scores takes the first n_seqs segments
-        return micro
 
     # ------------------------------------------------------------------ objective
     def _pair_loss(self, b: Dict, inv_pairs, slot: str):

@@ -34,7 +34,7 @@ import torch
 from ..data.collator import DataLoader, DistributedBatchSampler, SFTCollator
 from ..data.dataset import TokenizedDataset, cached_tokenize
 from .. import ops
-from ..models import CausalLM, apply_freeze_policy, build_model, get_config
+from ..models import CausalLM, apply_freeze_policy
 from ..models.lora import LoRAConfig
 from ..parallel.ddp import DDPEngine
 from ..parallel.process_group import all_reduce_sum_, all_reduce_sum_async, barrier, setup_distributed
@@ -42,6 +42,7 @@ from . import checkpoint as ckpt
 from .callbacks import (AimCallback, CallbackHandler, JSONLLoggerCallback, PrinterCallback, TrainerCallback,
                         TrainerControl, TrainerState)
 from .config import SFTConfig
+from .frozen import resolve_model, resolve_resume, tmp_sibling, to_device
 from .optim import FlatAdamW, LRScheduler, ShardedAdamW, get_schedule
 from ..utils.faults import maybe_inject
 
@@ -91,16 +92,9 @@ class SFTTrainer:
             from ..utils.gemm_tuning import enable_tuned_gemms
             enable_tuned_gemms()
         # ------------------------------------------------------------ model
-        if isinstance(model, str):
-            if os.path.isdir(model) and any(f.endswith(".safetensors") for f in os.listdir(model)):
-                model = ckpt.from_pretrained(model, device=dev, dtype=torch.bfloat16)
-            else:
-                model = build_model(get_config(model), device=dev, dtype=torch.bfloat16, seed=model_init_seed)
+        model = resolve_model(model, dev, seed=model_init_seed)
         assert isinstance(model, CausalLM), "SFTTrainer expects a CausalLM (or a preset name / HF dir)"
-        if next(model.parameters()).device != dev:
-            model.to(dev)
-            model.inv_freq = model.inv_freq.to(dev)
-        self.model = model
+        self.model = to_device(model, dev)
         if peft_config is not None or args.freeze_policy != "full":
             lc = peft_config or LoRAConfig(r=args.lora_r, lora_alpha=args.lora_alpha, lora_dropout=args.lora_dropout,
                                            **({"target_modules": args.lora_target_modules} if args.lora_target_modules else {}))
@@ -128,6 +122,7 @@ class SFTTrainer:
         self.collator = data_collator or SFTCollator(pad_id, pad_mult, args.max_length, self.packed,
                                                      args.per_device_train_batch_size * (args.max_length or 1024)
                                                      if args.packing else None)
+        self.eval_collator = None  # set by a trainer whose collators carry per-set data; None: self.collator serves both
         # ------------------------------------------------------------ engine + optimizer
         shard = bool(args.shard_optimizer_state) and self.dist.world_size > 1
         link, self.link_points = None, []
@@ -219,7 +214,7 @@ class SFTTrainer:
         tdir = os.path.join(cache, "tokenizer")
         if self.dist.is_main:
             tk = load_tokenizer()
-            tmp = f"{tdir}.tmp{os.getpid()}"
+            tmp = tmp_sibling(tdir)
             tk.save_pretrained(tmp)
             if os.path.isdir(tdir):
                 import shutil
@@ -253,8 +248,8 @@ class SFTTrainer:
         a = self.args
         s = DistributedBatchSampler(len(self.eval_dataset), a.per_device_eval_batch_size, self.dp_size,
                                     self.dp_rank, shuffle=False, drop_last=a.dataloader_drop_last)
-        return DataLoader(self.eval_dataset, self.collator, s, self.dist.device, a.dataloader_pin_memory,
-                          a.prefetch_batches)
+        return DataLoader(self.eval_dataset, self.eval_collator or self.collator, s, self.dist.device,
+                          a.dataloader_pin_memory, a.prefetch_batches)
 
     # ------------------------------------------------------------------ core step
     def _objective(self) -> Dict:
@@ -530,19 +525,16 @@ class SFTTrainer:
         self.state.num_train_epochs = math.ceil(max_steps / steps_per_epoch)
         self.state.train_batch_size = a.per_device_train_batch_size
         start_epoch, skip_batches = 0, 0
-        resume = resume_from_checkpoint or a.resume_from_checkpoint
+        resume = resolve_resume(a, resume_from_checkpoint)
         if resume:
-            if resume is True or resume == "auto":
-                resume = ckpt.latest_checkpoint(a.output_dir)
-            if resume:
-                with self.heartbeat.hold("ckpt_load"):
-                    st, _ = ckpt.load_checkpoint(resume, self.model, self.optimizer, self.scheduler, self.dist.rank)
-                st.is_world_process_zero = self.dist.is_main
-                self.state = st
-                start_epoch = self.state.global_step // steps_per_epoch
-                skip_batches = (self.state.global_step % steps_per_epoch) * ga
-                if self.dist.is_main:
-                    print(f"[trainer] resumed from {resume} at step {self.state.global_step}", flush=True)
+            with self.heartbeat.hold("ckpt_load"):
+                st, _ = ckpt.load_checkpoint(resume, self.model, self.optimizer, self.scheduler, self.dist.rank)
+            st.is_world_process_zero = self.dist.is_main
+            self.state = st
+            start_epoch = self.state.global_step // steps_per_epoch
+            skip_batches = (self.state.global_step % steps_per_epoch) * ga
+            if self.dist.is_main:
+                print(f"[trainer] resumed from {resume} at step {self.state.global_step}", flush=True)
         if self.dist.is_main:
             print(f"[trainer] world={self.dist.world_size} device={self.dist.device} trainable="
                   f"{self.trainable_params:,}/{self.total_params:,} "
