@@ -143,6 +143,9 @@ TORCH_LIBRARY(sftamd, m) {
   // forward-layout GEMM C = a w^T with fused epilogues (csrc/gemm_tn.hip)
   m.def("gemm_tn(Tensor a, Tensor w, int cfg=11) -> Tensor");
   m.def("gemm_tn_swiglu(Tensor x, Tensor w_gate_up, int cfg=11) -> (Tensor, Tensor)");
+  // decode GEMM y = x w^T for 1 <= M <= 64, K % 64 == 0, N % 16 == 0: weight-streaming, rows independent of M
+  // (csrc/gemm_skinny.hip)
+  m.def("gemm_skinny(Tensor x, Tensor w) -> Tensor");
   m.def("gemm_tn_rope(Tensor x, Tensor w, Tensor cos, Tensor sin, int rope_cols, int cfg=11) -> Tensor");
   // optimizer
   m.def("sumsq(Tensor x) -> Tensor");

@@ -92,7 +92,7 @@ def _run_layers(model, ids: torch.Tensor, pos: torch.Tensor, attend):
 def _logits(model, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
     """Final norm and lm_head over the given rows of a ``_run_layers`` result: fp32 logits [rows, V]."""
     h, _ = ops.add_rms_norm(x, residual, model.model.norm.weight, model.config.rms_norm_eps)
-    return torch.nn.functional.linear(h, model.lm_head_weight).float()
+    return ops.linear(h, model.lm_head_weight).float()
 
 
 @torch.no_grad()

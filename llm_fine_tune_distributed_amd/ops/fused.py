@@ -491,9 +491,30 @@ def _fwd_on_hip(x2d: torch.Tensor, w: torch.Tensor) -> bool:
     return (w.shape[0], x2d.shape[0], x2d.shape[1]) not in tuned_tn_shapes() or x2d.stride(0) != x2d.shape[1]
 
 
+# The decode GEMM is the route for all of its M <= 64, although a SmolLM3-3B decode step on it is 1.47 x / 1.30 x /
+# 1.02 x the library's at B = 1 / 16 / 32 and only 0.98 x / 0.99 x at B = 48 / 64 (profiles/gemm_skinny.md): its rows
+# are bit for bit independent of M, so a prompt prefilled alone (M = its length) and inside a batch (M = the batch's
+# tokens) gets the same projections, and generate_batch(...)[b] == generate(...) holds by construction. A route cut at
+# M = 32 puts the two on different kernels with different rounding (tests/test_qwen2_gpu.py caught it).
+
+
+def _skinny_ok(x2d: torch.Tensor, w: torch.Tensor) -> bool:
+    """Shapes the weight-streaming decode GEMM (csrc/gemm_skinny.hip) is routed: the rows of a generation step."""
+    M, K = x2d.shape
+    return (_ext.use_hip(x2d) and x2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.dim() == 2
+            and 1 <= M <= 64 and w.shape[1] == K and K % 64 == 0 and K > 0
+            and w.shape[0] % 16 == 0 and w.shape[0] > 0 and w.numel() < 2 ** 31 and w.is_contiguous()
+            and x2d.stride(1) == 1
+            and (M == 1 or (x2d.stride(0) % 8 == 0 and x2d.stride(0) >= K))
+            and x2d.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+
+
 def fwd_gemm(x2d: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """y = x2d @ w^T for a plain projection forward: hipBLASLt for shapes with a TunableOp selection, the
-    row-contiguous HIP kernel (csrc/gemm_tn.hip tn6) otherwise (see _FWD_GEMM)."""
+    """y = x2d @ w^T for a plain projection forward: the decode GEMM (csrc/gemm_skinny.hip) for M <= 64, else hipBLASLt
+    for shapes with a TunableOp selection and the row-contiguous HIP kernel (csrc/gemm_tn.hip tn6) otherwise (see
+    _FWD_GEMM; blas forces the library for every M)."""
+    if _FWD_GEMM != "blas" and _skinny_ok(x2d, w):
+        return _ext.ops().gemm_skinny(x2d, w)
     if _fwd_on_hip(x2d, w):
         return _ext.ops().gemm_tn(x2d, w, _ROWC_CFG)
     return torch.nn.functional.linear(x2d, w)
