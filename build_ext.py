@@ -31,11 +31,12 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
-# Extra hipcc flags per source file. attention_d64.hip and gemm_skinny.hip are compiled without the packed fp32 VALU
-# instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): the accumulator rescales and softmax arithmetic of the
-# first, the accumulator sums of the second stay scalar fp32 ops.
+# Extra hipcc flags per source file. attention_d64.hip, decode_attention_d64.hip and gemm_skinny.hip are compiled
+# without the packed fp32 VALU instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): the accumulator rescales and
+# softmax arithmetic of the first two, the accumulator sums of the third stay scalar fp32 ops.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_HIP_FLAGS = {"attention_d64.hip": _NO_PK_F32, "gemm_skinny.hip": _NO_PK_F32}
+EXTRA_HIP_FLAGS = {"attention_d64.hip": _NO_PK_F32, "decode_attention_d64.hip": _NO_PK_F32,
+                   "gemm_skinny.hip": _NO_PK_F32}
 
 
 def torch_paths():

@@ -9,7 +9,12 @@
 //
 // decode_attention_batched runs the same step for B sequences at once: grid (splits, kv_heads, B), each block
 // reading its own sequence's length, after an append kernel has stored the step's K/V rows in the caches.
+//
+// The split kernels below are the head_dim-128 ones. At head_dim 64 the two ops launch the MFMA split kernels of
+// csrc/decode_attention_d64.hip instead (same grid, same partials); the append and combine kernels are templates on the
+// head dimension and serve both.
 #include "common.h"
+#include "decode_attention_d64.h"
 
 namespace sftamd {
 namespace decode {
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(256) void split_kernel(const u16* __restrict__ q, c
 }
 
 // Merge of one query head's splits. EMPTY_OK: a sequence with no live key (every chunk empty) gives zeros, not 0/0.
-template <bool EMPTY_OK>
+template <bool EMPTY_OK, int HD>
 __device__ __forceinline__ void combine_body(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                              u16* __restrict__ out, const int hq, int nq, int nkv, int splits) {
   const int d = threadIdx.x;
@@ -139,33 +144,35 @@ __device__ __forceinline__ void combine_body(const float* __restrict__ part_o, c
     if (ms == -INFINITY) continue;
     const float w = exp2f(ms - M);
     L += w * part_ml[b * 2 + 1];
-    O += w * part_o[b * D + d];
+    O += w * part_o[b * HD + d];
   }
   if (EMPTY_OK && L == 0.f) {
-    out[(long)hq * D + d] = 0;
+    out[(long)hq * HD + d] = 0;
     return;
   }
-  out[(long)hq * D + d] = f2bf(O / L);
+  out[(long)hq * HD + d] = f2bf(O / L);
 }
 
-__global__ __launch_bounds__(128) void combine_kernel(const float* __restrict__ part_o,
-                                                      const float* __restrict__ part_ml, u16* __restrict__ out,
-                                                      int nq, int nkv, int splits) {
-  combine_body<false>(part_o, part_ml, out, blockIdx.x, nq, nkv, splits);
+template <int HD>
+__global__ __launch_bounds__(HD) void combine_kernel(const float* __restrict__ part_o,
+                                                     const float* __restrict__ part_ml, u16* __restrict__ out,
+                                                     int nq, int nkv, int splits) {
+  combine_body<false, HD>(part_o, part_ml, out, blockIdx.x, nq, nkv, splits);
 }
 
 // ---- batched decode: B sequences, one slab [S_max, nkv, D] each, one step's packed qkv row each -----------------
 
 // Row b's K and V of this step -> cache[b, lens[b] - 1]. One block per sequence, 16-byte loads and stores.
 // A length outside (0, S_max] skips the row: a host bug must not become an out-of-bounds write.
+template <int HD>
 __global__ __launch_bounds__(256) void append_kernel(const u16* __restrict__ qkv, u16* __restrict__ kc,
                                                      u16* __restrict__ vc, const int* __restrict__ lens, int nq,
                                                      int nkv, int smax) {
   const int b = blockIdx.x;
   const int len = lens[b];
   if (len <= 0 || len > smax) return;
-  const int nvec = nkv * D / 8;  // uint4 per K (and per V) row
-  const uint4* src = (const uint4*)(qkv + (long)b * (nq + 2 * nkv) * D + (long)nq * D);
+  const int nvec = nkv * HD / 8;  // uint4 per K (and per V) row
+  const uint4* src = (const uint4*)(qkv + (long)b * (nq + 2 * nkv) * HD + (long)nq * HD);
   const long row = ((long)b * smax + (len - 1)) * nvec;
   uint4* kd = (uint4*)kc + row;
   uint4* vd = (uint4*)vc + row;
@@ -190,46 +197,75 @@ __global__ __launch_bounds__(256) void split_batched_kernel(const u16* __restric
 }
 
 // grid (nq, B)
-__global__ __launch_bounds__(128) void combine_batched_kernel(const float* __restrict__ part_o,
-                                                              const float* __restrict__ part_ml,
-                                                              u16* __restrict__ out, int nq, int nkv, int splits) {
+template <int HD>
+__global__ __launch_bounds__(HD) void combine_batched_kernel(const float* __restrict__ part_o,
+                                                             const float* __restrict__ part_ml,
+                                                             u16* __restrict__ out, int nq, int nkv, int splits) {
   const int b = blockIdx.y;
-  combine_body<true>(part_o + (long)b * nq * splits * D, part_ml + (long)b * nq * splits * 2,
-                     out + (long)b * nq * D, blockIdx.x, nq, nkv, splits);
+  combine_body<true, HD>(part_o + (long)b * nq * splits * HD, part_ml + (long)b * nq * splits * 2,
+                         out + (long)b * nq * HD, blockIdx.x, nq, nkv, splits);
 }
 
 }  // namespace decode
+
+// The head dimension of a cache, which picks the split kernels: 128 (scalar, this file) or 64 (MFMA,
+// csrc/decode_attention_d64.hip). The head_dim-64 kernels have no sliding window.
+static int64_t cache_head_dim(const char* op, const at::Tensor& kcache, int64_t window) {
+  const int64_t hd = kcache.size(-1);
+  SFT_CHECK(hd == decode64::D || hd == decode::D, op, ": the cache's head_dim is ", hd,
+            ", the decode kernels are built for ", decode64::D, " and ", decode::D);
+  SFT_CHECK(window >= 0, op, ": window must be >= 0");
+  SFT_CHECK(hd == decode::D || window == 0, op, ": no sliding window at head_dim ", decode64::D);
+  return hd;
+}
+
+static bool aligned16(const at::Tensor& t) { return (uintptr_t)t.data_ptr() % 16 == 0; }
 
 at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
                             const at::Tensor& cache_len, int64_t nq, int64_t nkv, double scale, int64_t window) {
   SFT_CHECK_BF16(q);
   SFT_CHECK_BF16(kcache);
   SFT_CHECK(q.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous(), "contiguous");
-  SFT_CHECK(kcache.dim() == 3 && kcache.size(1) == nkv && kcache.size(2) == decode::D, "kcache [S, nkv, 128]");
-  SFT_CHECK(q.numel() == nq * decode::D, "q must be [nq*128]");
+  SFT_CHECK(kcache.dim() == 3 && kcache.size(1) == nkv, "kcache [S, nkv, head_dim]");
+  const int64_t hd = cache_head_dim("decode_attention", kcache, window);
+  SFT_CHECK(q.numel() == nq * hd, "q must be [nq * head_dim]");
   SFT_CHECK(nq % nkv == 0 && nq / nkv <= decode::MAXREP, "GQA ratio <= 8");
   SFT_CHECK(cache_len.scalar_type() == at::kInt && cache_len.is_cuda(), "cache_len int32 on device");
-  SFT_CHECK(window >= 0, "decode_attention: window must be >= 0");
   const int smax = kcache.size(0);
   const int win = window < smax ? (int)window : 0;  // a window that covers the cache is no window
   const int splits = (smax + decode::CHUNK - 1) / decode::CHUNK;
   const int rep = nq / nkv;
-  auto po = at::empty({nkv * splits * rep * decode::D}, q.options().dtype(at::kFloat));
+  auto po = at::empty({nkv * splits * rep * hd}, q.options().dtype(at::kFloat));
   auto pml = at::empty({nkv * splits * rep * 2}, q.options().dtype(at::kFloat));
-  auto out = at::empty({nq * decode::D}, q.options());
+  auto out = at::empty({nq * hd}, q.options());
+  if (hd == decode64::D) {
+    SFT_CHECK_CUDA(q);
+    SFT_CHECK_BF16(vcache);
+    SFT_CHECK(vcache.sizes() == kcache.sizes() && kcache.is_cuda() && vcache.is_cuda(), "vcache must match kcache");
+    SFT_CHECK(smax >= 1 && nq > 0 && nkv > 0 && nkv <= 65535, "empty cache or head counts");
+    SFT_CHECK(aligned16(q) && aligned16(kcache) && aligned16(vcache), "16-byte aligned");
+    SFT_TRACE("decode.d64");
+    decode64::launch_split((const u16*)q.data_ptr(), (const u16*)kcache.data_ptr(), (const u16*)vcache.data_ptr(),
+                           cache_len.data_ptr<int>(), po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, smax,
+                           (float)scale * decode::LOG2E, cur_stream());
+    decode::combine_kernel<decode64::D><<<nq, decode64::D, 0, cur_stream()>>>(
+        po.data_ptr<float>(), pml.data_ptr<float>(), (u16*)out.data_ptr(), nq, nkv, splits);
+    SFT_LAUNCH_CHECK();
+    return out;
+  }
   decode::split_kernel<<<dim3(splits, nkv), 256, 0, cur_stream()>>>(
       (const u16*)q.data_ptr(), (const u16*)kcache.data_ptr(), (const u16*)vcache.data_ptr(), cache_len.data_ptr<int>(),
       po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, (float)scale * decode::LOG2E, win);
   SFT_LAUNCH_CHECK();
-  decode::combine_kernel<<<nq, 128, 0, cur_stream()>>>(po.data_ptr<float>(), pml.data_ptr<float>(),
-                                                       (u16*)out.data_ptr(), nq, nkv, splits);
+  decode::combine_kernel<decode::D><<<nq, decode::D, 0, cur_stream()>>>(po.data_ptr<float>(), pml.data_ptr<float>(),
+                                                                        (u16*)out.data_ptr(), nq, nkv, splits);
   SFT_LAUNCH_CHECK();
   return out;
 }
 
 // One decode step of B sequences: append row b's K/V at cache[b, lens[b] - 1], then attend over cache[b, :lens[b]].
-// qkv [B, (nq + 2 nkv) * 128] (post-RoPE), kcache / vcache [B, S_max, nkv, 128], lens int32 [B] on the device
-// (live length INCLUDING the token being decoded). Static shapes, no host sync: lives inside a captured graph.
+// qkv [B, (nq + 2 nkv) * D] (post-RoPE), kcache / vcache [B, S_max, nkv, D] with D = 64 or 128, lens int32 [B] on the
+// device (live length INCLUDING the token being decoded). Static shapes, no host sync: lives inside a captured graph.
 at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at::Tensor vcache, const at::Tensor& lens,
                                     int64_t nq, int64_t nkv, double scale, int64_t window) {
   SFT_CHECK_CUDA(qkv);
@@ -238,34 +274,45 @@ at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at
   SFT_CHECK_BF16(vcache);
   SFT_CHECK(qkv.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous(), "contiguous");
   SFT_CHECK(nq > 0 && nkv > 0 && nq % nkv == 0 && nq / nkv <= decode::MAXREP, "GQA ratio <= 8");
-  SFT_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * decode::D, "qkv must be [B, (nq + 2 nkv) * 128]");
+  SFT_CHECK(kcache.dim() == 4, "kcache [B, S, nkv, head_dim]");
+  const int64_t hd = cache_head_dim("decode_attention_batched", kcache, window);
+  SFT_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * hd, "qkv must be [B, (nq + 2 nkv) * head_dim]");
   const int64_t B = qkv.size(0);
-  SFT_CHECK(kcache.dim() == 4 && kcache.size(0) == B && kcache.size(2) == nkv && kcache.size(3) == decode::D,
-            "kcache [B, S, nkv, 128]");
+  SFT_CHECK(kcache.size(0) == B && kcache.size(2) == nkv, "kcache [B, S, nkv, head_dim]");
   SFT_CHECK(vcache.sizes() == kcache.sizes() && kcache.is_cuda() && vcache.is_cuda(), "vcache must match kcache");
   SFT_CHECK(lens.scalar_type() == at::kInt && lens.is_cuda() && lens.is_contiguous() && lens.numel() == B,
             "lens int32 [B] on device");
-  SFT_CHECK(B >= 1 && B <= 65535, "batch size");
-  SFT_CHECK((uintptr_t)qkv.data_ptr() % 16 == 0 && (uintptr_t)kcache.data_ptr() % 16 == 0 &&
-                (uintptr_t)vcache.data_ptr() % 16 == 0, "16-byte aligned");
+  SFT_CHECK(B >= 1 && B <= 65535 && nkv <= 65535, "batch size");
+  SFT_CHECK(aligned16(qkv) && aligned16(kcache) && aligned16(vcache), "16-byte aligned");
   const int smax = kcache.size(1);
   SFT_CHECK(smax >= 1, "empty cache");
-  SFT_CHECK(window >= 0, "decode_attention_batched: window must be >= 0");
   const int win = window < smax ? (int)window : 0;  // a window that covers the slab is no window
   const int splits = (smax + decode::CHUNK - 1) / decode::CHUNK;
   const int rep = nq / nkv;
-  auto po = at::empty({B * nkv * splits * rep * decode::D}, qkv.options().dtype(at::kFloat));
+  auto po = at::empty({B * nkv * splits * rep * hd}, qkv.options().dtype(at::kFloat));
   auto pml = at::empty({B * nkv * splits * rep * 2}, qkv.options().dtype(at::kFloat));
-  auto out = at::empty({B, nq * decode::D}, qkv.options());
-  decode::append_kernel<<<B, 256, 0, cur_stream()>>>((const u16*)qkv.data_ptr(), (u16*)kcache.data_ptr(),
-                                                     (u16*)vcache.data_ptr(), lens.data_ptr<int>(), nq, nkv, smax);
+  auto out = at::empty({B, nq * hd}, qkv.options());
+  const u16* qp = (const u16*)qkv.data_ptr();
+  u16 *kp = (u16*)kcache.data_ptr(), *vp = (u16*)vcache.data_ptr();
+  if (hd == decode64::D) {
+    SFT_TRACE("decode.d64");
+    decode::append_kernel<decode64::D><<<B, 256, 0, cur_stream()>>>(qp, kp, vp, lens.data_ptr<int>(), nq, nkv, smax);
+    SFT_LAUNCH_CHECK();
+    decode64::launch_split_batched(qp, kp, vp, lens.data_ptr<int>(), po.data_ptr<float>(), pml.data_ptr<float>(), B,
+                                   nq, nkv, smax, (float)scale * decode::LOG2E, cur_stream());
+    decode::combine_batched_kernel<decode64::D><<<dim3(nq, B), decode64::D, 0, cur_stream()>>>(
+        po.data_ptr<float>(), pml.data_ptr<float>(), (u16*)out.data_ptr(), nq, nkv, splits);
+    SFT_LAUNCH_CHECK();
+    return out;
+  }
+  decode::append_kernel<decode::D><<<B, 256, 0, cur_stream()>>>(qp, kp, vp, lens.data_ptr<int>(), nq, nkv, smax);
   SFT_LAUNCH_CHECK();
   decode::split_batched_kernel<<<dim3(splits, nkv, B), 256, 0, cur_stream()>>>(
-      (const u16*)qkv.data_ptr(), (const u16*)kcache.data_ptr(), (const u16*)vcache.data_ptr(), lens.data_ptr<int>(),
-      po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, smax, (float)scale * decode::LOG2E, win);
+      qp, kp, vp, lens.data_ptr<int>(), po.data_ptr<float>(), pml.data_ptr<float>(), nq, nkv, smax,
+      (float)scale * decode::LOG2E, win);
   SFT_LAUNCH_CHECK();
-  decode::combine_batched_kernel<<<dim3(nq, B), 128, 0, cur_stream()>>>(po.data_ptr<float>(), pml.data_ptr<float>(),
-                                                                        (u16*)out.data_ptr(), nq, nkv, splits);
+  decode::combine_batched_kernel<decode::D><<<dim3(nq, B), decode::D, 0, cur_stream()>>>(
+      po.data_ptr<float>(), pml.data_ptr<float>(), (u16*)out.data_ptr(), nq, nkv, splits);
   SFT_LAUNCH_CHECK();
   return out;
 }

@@ -55,6 +55,12 @@ def _windows(model) -> List[int]:
     return [layer.self_attn.window for layer in model.model.layers]
 
 
+def _hip_decode(model, t: torch.Tensor) -> bool:
+    """Whether generation takes the device path (graph decoder, HIP decode attention, device samplers): on the GPU
+    with the extension in use, at a head_dim the decode attention kernels are built for."""
+    return t.device.type == "cuda" and model.config.head_dim in (64, 128) and ops.use_hip(t)
+
+
 def _kv_rows(cfg, qkv: torch.Tensor):
     """The k and v columns of the packed qkv [M, (nq + 2 nkv) D] as [M, nkv, D] views."""
     nq, nkv, D = _heads(cfg)
@@ -277,7 +283,7 @@ def generate(model, prompt_ids: List[int], max_new_tokens: int = 256, eos_token_
     g = torch.Generator(device=dev).manual_seed(seed) if seed is not None else None
     ids = torch.tensor(prompt_ids, device=dev)
     logits = forward_cached(model, ids, cache, prefill=True)
-    gpu_path = dev.type == "cuda" and model.config.head_dim == 128 and ops.use_hip(ids)
+    gpu_path = _hip_decode(model, ids)
     dec = GraphDecoder(model, cache) if gpu_path else None
     graph = gpu_path if use_graph is None else (use_graph and gpu_path)
     if device_sampling is None:
@@ -493,7 +499,7 @@ def generate_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, e
     cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev,
                          model.model.embed_tokens.dtype)
     logits = prefill_batch(model, prompts, cache)
-    gpu_path = dev.type == "cuda" and model.config.head_dim == 128 and ops.use_hip(logits)
+    gpu_path = _hip_decode(model, logits)
     graph = gpu_path if use_graph is None else (use_graph and gpu_path)
     dec = BatchGraphDecoder(model, cache)
     if device_sampling is None:
@@ -581,7 +587,7 @@ def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eo
         cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev,
                              model.model.embed_tokens.dtype)
         logits = prefill_batch(model, prompts, cache)
-        gpu_path = dev.type == "cuda" and model.config.head_dim == 128 and ops.use_hip(logits)
+        gpu_path = _hip_decode(model, logits)
         graph = gpu_path if use_graph is None else (use_graph and gpu_path)
         dec = BatchGraphDecoder(model, cache)
         if device_sampling is None:

@@ -1896,7 +1896,9 @@ def lora_linear(x, weight, lora) -> torch.Tensor:
 
 def decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, scale=None, window=0):
     """Single-token GQA attention over cache[:cache_len] (cache_len: int32 device tensor); with a sliding window
-    W > 0 over its last W rows, cache[max(0, cache_len - W):cache_len]."""
+    W > 0 over its last W rows, cache[max(0, cache_len - W):cache_len]. The HIP op is built for head_dim 128
+    (csrc/decode_attention.hip) and 64 (csrc/decode_attention_d64.hip: MFMA kernels, no sliding window) and raises on
+    any other."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.numel() // n_q)
     window = _window(window, True)
     if _ext.use_hip(q):
@@ -1915,11 +1917,12 @@ def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None, w
     sequence INCLUDING the token being decoded. Row b's K/V are appended at ``cache[b, lens[b] - 1]`` (a length
     outside (0, S_max] skips the row), then row b attends over ``cache[b, :lens[b]]`` (with a sliding ``window``
     W > 0 over its last W rows, ``cache[b, max(0, lens[b] - W):lens[b]]``). Returns [B, n_q * D].
-    The HIP kernel is built for head_dim 128; other head dims decode in torch, as they do in forward_cached."""
+    The HIP kernels are built for head_dim 128 (csrc/decode_attention.hip) and 64 (csrc/decode_attention_d64.hip: MFMA
+    kernels, no sliding window); other head dims decode in torch, as they do in forward_cached."""
     B = qkv.shape[0]
     D = qkv.shape[1] // (n_q + 2 * n_kv)
     window = _window(window, True)
-    if _ext.use_hip(qkv) and D == 128:
+    if _ext.use_hip(qkv) and D in (64, 128):
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
         return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale), window)
     out = torch.zeros(B, n_q * D, dtype=qkv.dtype, device=qkv.device)

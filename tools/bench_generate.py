@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Decode throughput of batched generation against sequential generation (SmolLM3-3B, random weights).
+"""Decode throughput of batched generation against sequential generation (SmolLM3-3B by default, any preset with
+``--model``; random weights).
 
-    python tools/bench_generate.py [--batches 1 4 16 64] [--reps 3] [--out table.md]
+    python tools/bench_generate.py [--model llama3.2-1b] [--batches 1 4 16 64] [--reps 3] [--out table.md]
 
 For every batch size B two arms are timed, alternating, each as a fresh child process under its own ``timeout``:
 ``seq`` runs B sequential ``generate`` calls, ``batch`` one ``generate_batch`` of B. Prompt 128 tokens, 128 new
@@ -28,14 +29,14 @@ if ROOT not in sys.path:
 PROMPT, NEW = 128, 128
 
 
-def run_arm(arm: str, B: int, reps: int) -> dict:
+def run_arm(arm: str, B: int, reps: int, model_name: str = "smollm3-3b") -> dict:
     import torch
     from llm_fine_tune_distributed_amd.inference.generation import generate, generate_batch
-    from llm_fine_tune_distributed_amd.models import build_model, smollm3_3b
+    from llm_fine_tune_distributed_amd.models import build_model, get_config
     from llm_fine_tune_distributed_amd.ops import _ext
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
     assert _ext.load(), _ext.load_error()
-    cfg = smollm3_3b()
+    cfg = get_config(model_name)
     model = build_model(cfg, device="cuda", dtype=torch.bfloat16, seed=0)
     g = torch.Generator().manual_seed(1)
     prompts = [torch.randint(0, cfg.vocab_size, (PROMPT,), generator=g).tolist() for _ in range(B)]
@@ -58,7 +59,7 @@ def run_arm(arm: str, B: int, reps: int) -> dict:
         times.append(time.perf_counter() - t0)
     best = min(times)
     return {"arm": arm, "batch": B, "new_tokens": B * NEW, "seconds": times, "tokens_per_s": B * NEW / best,
-            "device": torch.cuda.get_device_name(0), "layers": cfg.num_hidden_layers}
+            "device": torch.cuda.get_device_name(0), "layers": cfg.num_hidden_layers, "model": model_name}
 
 
 def kernel_split(path: str) -> str:
@@ -80,7 +81,7 @@ def kernel_split(path: str) -> str:
         us = (e - s) / 1e3
         if "Cijk" in n or "gemm" in n.lower() or "gemv" in n.lower():
             k = "GEMMs"
-        elif "decode::" in n:
+        elif "decode::" in n or "decode64::" in n:
             k = "decode attention"
         elif "samp::" in n:
             k = "sampler"
@@ -102,6 +103,7 @@ def kernel_split(path: str) -> str:
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="smollm3-3b", help="model preset (models.get_config)")
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4, 16, 64])
     ap.add_argument("--arm", choices=["seq", "batch"], help="run one arm in this process and print one JSON line")
     ap.add_argument("--batch", type=int, default=16)
@@ -114,13 +116,13 @@ def main(argv=None):
         print(kernel_split(a.kernel_split))
         return
     if a.arm:
-        print(json.dumps(run_arm(a.arm, a.batch, a.reps)))
+        print(json.dumps(run_arm(a.arm, a.batch, a.reps, a.model)))
         return
     results = {}
     for B in a.batches:
         for arm in ("seq", "batch"):  # alternate the arms: neighbours in time share the box's condition
             cmd = ["timeout", "-k", "10", str(a.arm_timeout), sys.executable, os.path.abspath(__file__), "--arm", arm,
-                   "--batch", str(B), "--reps", str(a.reps)]
+                   "--batch", str(B), "--reps", str(a.reps), "--model", a.model]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:  # a fault, an abort or the time limit: start nothing more on this GPU
                 sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
@@ -128,7 +130,8 @@ def main(argv=None):
             results[(B, arm)] = json.loads(r.stdout.strip().splitlines()[-1])
             print(json.dumps(results[(B, arm)]), flush=True)
     dev = results[(a.batches[0], "seq")]["device"]
-    lines = [f"Device: {dev}. SmolLM3-3B ({results[(a.batches[0], 'seq')]['layers']} layers), random bf16 weights, "
+    name = "SmolLM3-3B" if a.model == "smollm3-3b" else a.model
+    lines = [f"Device: {dev}. {name} ({results[(a.batches[0], 'seq')]['layers']} layers), random bf16 weights, "
              f"prompt {PROMPT}, {NEW} new tokens per sequence, greedy, no EOS.", "",
              "| B | sequential generate: s | tokens/s | generate_batch: s | tokens/s | ratio |",
              "|---:|---:|---:|---:|---:|---:|"]
