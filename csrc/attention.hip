@@ -924,6 +924,40 @@ static void launch_dkdv(const u16* qkv, const u16* dout, const float* lse, const
 #undef SFT_DKDV
 }
 
+// The rows no attention grid visits, written as +0 before the attention kernels run: block s < nseq takes the rows of
+// segment s at or past max_seqlen (none under the max_seqlen contract, see flash_fwd), block nseq the rows at or past
+// cu[nseq]. rows [total, ld] bf16 (ld % 8 == 0), lse [nq, total] fp32 or null. The debug build traps on a segment
+// longer than max_seqlen.
+__global__ __launch_bounds__(256) void unvisited_rows_kernel(const int* __restrict__ cu, int nseq, int total,
+                                                             int max_seqlen, u16* __restrict__ rows, long ld,
+                                                             float* __restrict__ lse, int nq) {
+  const int s = blockIdx.x;
+  int r0, r1;
+  if (s < nseq) {
+    const int start = cu[s], end = cu[s + 1];
+    SFT_DASSERT(end - start <= max_seqlen);
+    r0 = start + max_seqlen;
+    r1 = end;
+  } else {
+    r0 = cu[nseq];
+    r1 = total;
+  }
+  r0 = max(r0, 0);
+  r1 = min(r1, total);
+  if (r0 >= r1) return;
+  const long nvec = (long)(r1 - r0) * (ld / 8);
+  uint4* dst = reinterpret_cast<uint4*>(rows + (long)r0 * ld);
+  for (long i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (lse != nullptr)
+    for (long i = threadIdx.x; i < (long)nq * (r1 - r0); i += blockDim.x)
+      lse[(i / (r1 - r0)) * total + r0 + i % (r1 - r0)] = 0.f;
+}
+
+static void launch_unvisited_rows(const int* cu, int nseq, int total, int max_seqlen, u16* rows, long ld, float* lse,
+                                  int nq, hipStream_t st) {
+  unvisited_rows_kernel<<<nseq + 1, 256, 0, st>>>(cu, nseq, total, max_seqlen, rows, ld, lse, nq);
+}
+
 }  // namespace attn
 
 static void check_attn_args(const at::Tensor& qkv, const at::Tensor& cu, int64_t nq, int64_t nkv, int64_t hd,
@@ -955,6 +989,14 @@ static long attn_ds_budget() {
   return (e && e[0] ? atol(e) : 2048L) * 1024L * 1024L;
 }
 
+// The max_seqlen contract of flash_fwd / flash_bwd / flash_bwd_rope: cu holds nseq + 1 non-decreasing row offsets, the
+// segments [cu[s], cu[s + 1]) tile the rows [cu[0], cu[nseq]) of qkv, and every segment (a pad segment included) is at
+// most max_seqlen rows long: the query and key dimensions of every grid are sized from max_seqlen alone, and
+// the host never reads cu from the device. A longer segment is a caller error (its rows past max_seqlen hold no attention
+// result); callers check it where cu is on the host (ops.check_packed_meta) and the debug build traps on it. Rows at
+// or past cu[nseq] belong to no sequence: out, lse and dqkv hold +0 there (the collators' batches end with a pad
+// segment, so cu[nseq] == total in training). No row of out / lse / dqkv is left as the allocator returned it.
+//
 // forward: fwd32 (4 waves = HW GQA heads x 4 / HW 32-query blocks sharing each K / V tile)
 std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Tensor& cu, int64_t max_seqlen,
                                              int64_t nq, int64_t nkv, int64_t hd, double scale, bool causal,
@@ -965,9 +1007,13 @@ std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qkv, const at::Te
   const int nseq = cu.numel() - 1;
   auto out = at::empty({total, nq * hd}, qkv.options());
   auto lse = at::empty({nq, total}, qkv.options().dtype(at::kFloat));
-  if (total == 0 || max_seqlen == 0) return {out, lse};
-  const float sl2 = (float)scale * attn::LOG2E;
+  if (total == 0) return {out, lse};
   auto cu_c = cu.contiguous();
+  attn::launch_unvisited_rows(cu_c.data_ptr<int>(), nseq, total, (int)max_seqlen, (u16*)out.data_ptr(), nq * hd,
+                              lse.data_ptr<float>(), (int)nq, cur_stream());
+  SFT_LAUNCH_CHECK();
+  if (max_seqlen == 0) return {out, lse};
+  const float sl2 = (float)scale * attn::LOG2E;
   const u16* q = (const u16*)qkv.data_ptr();
   u16* o = (u16*)out.data_ptr();
   float* lp = lse.data_ptr<float>();
@@ -1014,7 +1060,12 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
   const int total = qkv.size(0);
   const int nseq = cu.numel() - 1;
   auto dqkv = at::empty_like(qkv);
-  if (total == 0 || max_seqlen == 0) return dqkv;
+  if (total == 0) return dqkv;
+  auto cu_c = cu.contiguous();
+  attn::launch_unvisited_rows(cu_c.data_ptr<int>(), nseq, total, (int)max_seqlen, (u16*)dqkv.data_ptr(),
+                              qkv.size(1), nullptr, (int)nq, cur_stream());
+  SFT_LAUNCH_CHECK();
+  if (max_seqlen == 0) return dqkv;
   at::Tensor delta;
   if (delta_in.has_value() && delta_in->defined()) {  // computed by the producer of dO (dgrad_gemm_delta's epilogue)
     delta = *delta_in;
@@ -1035,7 +1086,6 @@ static at::Tensor flash_bwd_impl(const at::Tensor& dout, const at::Tensor& qkv, 
     SFT_LAUNCH_CHECK();
   }
   const float sl2 = (float)scale * attn::LOG2E;
-  auto cu_c = cu.contiguous();
   const u16* q = (const u16*)qkv.data_ptr();
   const u16* dO = (const u16*)dout.data_ptr();
   if (hd == attn64::D) {  // (rope_done stays false: flash_bwd_rope runs the rope kernel on dqkv)

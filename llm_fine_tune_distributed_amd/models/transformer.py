@@ -537,7 +537,10 @@ class CausalLM(nn.Module):
             cu_seqlens = torch.tensor([0, M], dtype=torch.int32, device=dev)
             max_seqlen = M
         if max_seqlen is None:
+            # derived here (one device read): the maximum over ALL segments, as the attention ops require
             max_seqlen = int((cu_seqlens[1:] - cu_seqlens[:-1]).max().item())
+        elif cu_seqlens.device.type == "cpu":  # stated by the caller: checked where that costs no device read
+            ops.check_packed_meta(cu_seqlens, max_seqlen, M)
         if position_ids is None:
             position_ids = _positions_from_cu(cu_seqlens, M)
         if labels is not None:

@@ -1308,8 +1308,30 @@ def _window(window, causal) -> int:
     return window
 
 
+def check_packed_meta(cu_seqlens, max_seqlen, total=None) -> int:
+    """The attention ops' contract on a packed batch, checked on the host (``cu_seqlens``: a list or a CPU tensor; never
+    a device tensor, the check must not synchronise): offsets start at 0 and do not decrease, every segment, a pad
+    segment included, is at most ``max_seqlen`` rows (the kernels size their grids from max_seqlen alone and visit no row
+    past it), and with ``total`` the last offset is the number of rows. Returns max_seqlen; raises ValueError."""
+    if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.device.type != "cpu":
+        raise ValueError("check_packed_meta: cu_seqlens must be on the host")
+    cu = [int(v) for v in (cu_seqlens.tolist() if isinstance(cu_seqlens, torch.Tensor) else cu_seqlens)]
+    lens = [b - a for a, b in zip(cu[:-1], cu[1:])]
+    if len(cu) < 2 or cu[0] != 0 or min(lens) < 0:
+        raise ValueError(f"cu_seqlens must start at 0 and not decrease, got {cu[:8]}...")
+    if max(lens) > int(max_seqlen):
+        raise ValueError(f"max_seqlen={int(max_seqlen)} but segment {lens.index(max(lens))} of cu_seqlens has "
+                         f"{max(lens)} rows: max_seqlen is the maximum over all segments, a pad segment included")
+    if total is not None and cu[-1] != int(total):
+        raise ValueError(f"cu_seqlens ends at {cu[-1]} but the batch has {int(total)} rows: close it with a pad segment")
+    return int(max_seqlen)
+
+
 def flash_attention(qkv, cu_seqlens, max_seqlen, n_q, n_kv, head_dim, scale=None, causal=True, link=None, window=0):
-    """link: a fresh AttnLink shared with attn_out_linear (the o_proj on this output): the o_proj backward computes
+    """cu_seqlens / max_seqlen: every segment of cu_seqlens, a pad segment included, is at most max_seqlen rows long (a
+    longer one is a caller error: the kernels visit no row past max_seqlen; ``check_packed_meta`` checks it on the host,
+    the debug build on the device). Rows at or past cu_seqlens[-1] belong to no sequence: the output and the gradient
+    are +0 there. link: a fresh AttnLink shared with attn_out_linear (the o_proj on this output): the o_proj backward computes
     the attention backward's delta in its dgrad epilogue. window: W > 0 is a sliding window, the query at position
     i of its sequence sees the keys j with i - W < j <= i; 0 is no window."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)

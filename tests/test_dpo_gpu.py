@@ -370,7 +370,7 @@ def _model_batch(vocab):
         labels[c[s]:c[s] + k] = -100
     labels[c[4]:] = -100
     pos = torch.cat([torch.arange(b - a, device=DEV) for a, b in zip(c[:-1], c[1:])])
-    return dict(input_ids=ids, labels=labels, cu_seqlens=cu, position_ids=pos, max_seqlen=max(LENS), n_seqs=len(LENS))
+    return dict(input_ids=ids, labels=labels, cu_seqlens=cu, position_ids=pos, max_seqlen=max(max(LENS), ROWS - sum(LENS)), n_seqs=len(LENS))
 
 
 COEF = [0.83, -1.21, 0.37, -0.55]  # fixed weights of the linear objective sum_s c_s logp_s

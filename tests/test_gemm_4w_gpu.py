@@ -7,6 +7,7 @@ import torch
 
 from llm_fine_tune_distributed_amd.ops import _ext
 
+import _stale
 from _blockwise import assert_blocks_close, rounding_floor, swiglu_bwd_reference
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +72,7 @@ def test_wgrad_4wave_norm_slots(cfg, T, N, K, accumulate):
     slots[cap:] = 7.0
     # garbage in the caching allocator's free blocks: a hybrid launch parks the whole tiles' slots in an
     # uninitialised split-K buffer, every one of them must be written
-    torch.full((1 << 26,), float("nan"), device=DEV)
+    _stale.poison(_stale.NAN_FILL, 1 << 28)
     _ext.ops().wgrad_gemm(out, dy, x, accumulate, cfg, slots[:cap])
     want = out.float().pow(2).sum().item()
     assert abs(slots[:cap].sum().item() - want) <= 1e-3 * want

@@ -597,7 +597,7 @@ def _model_batch(vocab):
         labels[c[s]:c[s] + k] = -100
     labels[c[4]:] = -100
     pos = torch.cat([torch.arange(b - a, device=DEV) for a, b in zip(c[:-1], c[1:])])
-    return dict(input_ids=ids, labels=labels, cu_seqlens=cu, position_ids=pos, max_seqlen=max(LENS))
+    return dict(input_ids=ids, labels=labels, cu_seqlens=cu, position_ids=pos, max_seqlen=max(max(LENS), ROWS - sum(LENS)))
 
 
 def _policy_run(model, batch, extra, hip):

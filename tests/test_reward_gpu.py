@@ -347,7 +347,7 @@ def _model_batch(vocab):
     cu = cu_of(LENS, ROWS - sum(LENS))
     c = cu.tolist()
     pos = torch.cat([torch.arange(b - a, device=DEV) for a, b in zip(c[:-1], c[1:])])
-    return dict(input_ids=ids, cu_seqlens=cu, position_ids=pos, max_seqlen=max(LENS), n_seqs=len(LENS))
+    return dict(input_ids=ids, cu_seqlens=cu, position_ids=pos, max_seqlen=max(max(LENS), ROWS - sum(LENS)), n_seqs=len(LENS))
 
 
 def _score_run(model, batch, hip):

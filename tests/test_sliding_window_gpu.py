@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import _rowwise as rw
+import _stale
 from _blockwise import assert_blocks_close, block_rel_err
 from llm_fine_tune_distributed_amd.inference.generation import generate, generate_batch
 from llm_fine_tune_distributed_amd.models import build_model, get_config
@@ -106,12 +107,11 @@ def _grad_blocks(dqkv, want, r, what):
 
 
 def _poison_ds(lens, nq):
-    """A NaN-filled bf16 block of the dS^T size, allocated and freed: the caching allocator hands it to the backward's
-    at::empty, so a dS^T tile that bwd_dq32 reads and bwd_dkdv32 did not write shows as NaN instead of passing by the
-    luck of what the memory held."""
+    """Free memory filled with NaN bits (tests/_stale.py) at twice the dS^T size: the backward's at::empty gets a
+    poisoned block, so a dS^T tile that bwd_dq32 reads and bwd_dkdv32 did not write shows as NaN instead of passing by
+    the luck of what the memory held."""
     lp = (max(lens) + 127) // 128 * 128
-    t = torch.full((len(lens) * nq * lp * lp,), float("nan"), dtype=torch.bfloat16, device=DEV)
-    del t
+    _stale.poison(_stale.NAN_FILL, 2 * len(lens) * nq * lp * lp * 2)
 
 
 @pytest.mark.parametrize("ds_mb", ["", "0"])
