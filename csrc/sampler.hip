@@ -16,6 +16,8 @@
 //            counters (position, KV length, step) — the decode loop runs replay after replay.
 // sample_tokens is the same pair of launches for B rows (grid (tiles, B), then one merge block per row) with a
 // per-row finished flag: batched generation decodes many prompts per step.
+// That pair serves 1 <= top_k <= 64. top_k == 0 (nucleus alone, or no cut) and top_k > 64 go through the same two ops to
+// select_kernel below: an exact radix select of the cut values and a Gumbel-max draw, one workgroup per row.
 #include "common.h"
 
 #include <rocprim/block/block_radix_sort.hpp>
@@ -121,6 +123,29 @@ __global__ __launch_bounds__(NT) void partial_batched_kernel(const T* __restrict
                   cand_i + b * nc, blockIdx.x);
 }
 
+// What a drawn token writes (shared by final_body and select_kernel; every pointer is the row's own): the step counter
+// and last token, the next step's embedding input, the token log, the finished flag on ``eos`` (``done`` null: no
+// flag), else the advanced position / KV length, and the token's presence bit.
+__device__ __forceinline__ void commit_token(int tok, long long step, long long* __restrict__ state,
+                                             long long* __restrict__ tok_out, long long* __restrict__ pos_out,
+                                             int* __restrict__ len_out, long long* __restrict__ log, int log_cap,
+                                             unsigned* __restrict__ presence, int* __restrict__ done, int eos) {
+  state[0] = step + 1;
+  state[1] = tok;
+  if (tok_out) tok_out[0] = tok;
+  if (log && step < log_cap) log[step] = tok;
+  const bool finished = done != nullptr && tok == eos;
+  if (finished) *done = 1;
+  if (pos_out && !finished) {  // advance the decode step's position / KV length for the next replay
+    const long long p = state[2] + 1;
+    state[2] = p;
+    pos_out[0] = p;
+    state[3] = p + 1;
+    len_out[0] = (int)(p + 1);
+  }
+  atomicOr(presence + (tok >> 5), 1u << (tok & 31));
+}
+
 // The merge + draw of one row (shared by the single-row and the batched kernel); every pointer is the row's own.
 // ``done`` (batched only, else null) is the row's finished flag: drawing ``eos`` logs the token, sets the flag and
 // leaves position / KV length where they are (the EOS is never decoded).
@@ -181,20 +206,7 @@ __device__ __forceinline__ void final_body(const float* __restrict__ cand_v, con
       }
     }
   }
-  state[0] = step + 1;
-  state[1] = tok;
-  if (tok_out) tok_out[0] = tok;
-  if (log && step < log_cap) log[step] = tok;
-  const bool finished = done != nullptr && tok == eos;
-  if (finished) *done = 1;
-  if (pos_out && !finished) {  // advance the decode step's position / KV length for the next replay
-    const long long p = state[2] + 1;
-    state[2] = p;
-    pos_out[0] = p;
-    state[3] = p + 1;
-    len_out[0] = (int)(p + 1);
-  }
-  atomicOr(presence + (tok >> 5), 1u << (tok & 31));
+  commit_token(tok, step, state, tok_out, pos_out, len_out, log, log_cap, presence, done, eos);
 }
 
 __global__ __launch_bounds__(NT) void final_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
@@ -358,10 +370,271 @@ __global__ __launch_bounds__(NT) void full_final_kernel(const float* __restrict_
   *pw = *pw | (1u << (tok & 31));
 }
 
+// ---- the threshold sampler (sample_token / sample_tokens with top_k == 0 or top_k > 64): top-k and top-p cuts of any
+// size over the whole vocabulary, with no sort. z is the penalised logit / temperature, formed as above.
+//
+// The rule (value thresholds only, so it depends on no order and is deterministic):
+//   top-k (k > 0):   keep i when z_i >= t_k, t_k the k-th largest z of the row; every value equal to t_k is kept.
+//   top-p (p < 1):   over the survivors of the top-k cut, with softmax taken over those survivors, keep i when
+//                    M(z_i) <= p, M(v) the probability mass of the survivors STRICTLY greater than v (M(max) = 0: the
+//                    largest value always survives).
+// Without exact ties that is inference/generation.py sample_next token for token. With ties at the nucleus edge
+// sample_next has no defined answer (torch.sort is not stable); this rule keeps all the tied tokens.
+// The draw is sample_tokens_full's Gumbel-max restricted to the kept set: the same key z_i + g_i from the same uniform of
+// (step, seed + b, i), lowest index on a tie. So (k = 0, p = 1) draws what sample_tokens_full draws, and (k, p) draws
+// what it draws from the row masked to the kept set.
+//
+// Work split: ONE 1024-thread workgroup per row, no workspace in global memory, no global atomics. The workgroup
+// sweeps its row several times (the row stays in L2: 128k bf16 logits are 256 KB) and recomputes z each time:
+//   1 sweep      row maximum m (skipped when there is no cut at all);
+//   4 sweeps     per cut, an exact radix select of the edge value over key(z), the order-preserving 32-bit image of z
+//                (sign-flipped bits; -0 counts as +0). Level 1 buckets by distance from the maximum,
+//                bin = min(2047, floor(64 (m - z))): monotone in z like a digit, but it spreads the dense body of the
+//                row over hundreds of bins where the key's leading 11 bits (sign, exponent, 2 mantissa bits) would pile
+//                it onto a few dozen LDS addresses. Levels 2-4 take the 11 / 11 / 10 key bits of the tokens inside
+//                the chosen bin, so after level 4 the edge is one exact 32-bit value whatever the tie count.
+//   1 sweep      Gumbel arg-max over the tokens with key >= edge, then thread 0 writes what final_body writes.
+// So (0, 1) is 1 sweep, top-k alone or top-p alone 6, both 10.
+// LDS: one histogram of 2048 64-bit bins (16 KB), bin 0 the LARGEST values, filled with integer LDS atomics (order
+// cannot matter) and scanned by the workgroup (thread t owns bins 2t, 2t + 1). The top-k select counts (weight 1) and
+// picks the first bin whose inclusive count exceeds k - 1. The top-p select weighs token i with
+// floor(exp(z_i - m) 2^40), a fixed-point mass (a 2^18-token row sums below 2^58), restricted to key >= the top-k edge;
+// level 1's total is the survivors' mass S, the threshold is floor(p S), and the select picks the first bin whose
+// inclusive mass exceeds it, which is the bin of the smallest value v with M(v) <= p. The remainder (threshold minus
+// the mass above the bin) carries to the next level. A repeated call gives the same tokens bit for bit.
+namespace sel {
+
+constexpr int NT = 1024;
+constexpr int BINS = 2048;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ unsigned okey(float z) {
+  const unsigned u = __float_as_uint(z == 0.f ? 0.f : z);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// level-1 bin: distance below the row maximum in steps of 1/64, clamped (NaN and -inf land in the last bin)
+__device__ __forceinline__ int lin_bin(float m, float z) { return (int)fminf((m - z) * 64.f, (float)(BINS - 1)); }
+
+// fixed-point exp(z - m) 2^40; below e^-40 (or NaN) it is 0
+__device__ __forceinline__ u64 mass_of(float m, float z) {
+  const float d = m - z;
+  return (d >= 0.f && d < 40.f) ? (u64)(__expf(0.f - d) * 1099511627776.f) : 0ull;
+}
+
+// fn(i, x_i, z_i) for every token of the row (x the penalised logit, z = x / temperature), thread t taking the 8-token
+// runs t, t + 1024, ...
+template <typename T, typename F>
+__device__ __forceinline__ void sweep(const T* __restrict__ row, int V, const unsigned* __restrict__ pres_row,
+                                      float inv_temp, float penalty, F&& fn) {
+  const int runs = (V + IPT - 1) / IPT;
+  for (int c = threadIdx.x; c < runs; c += NT) {
+    const int i0 = c * IPT;
+    float raw[IPT];
+    load_run<T>(row, i0, V, raw);
+    const unsigned pres = penalty != 1.f ? (pres_row[i0 >> 5] >> (i0 & 31)) & 0xffu : 0u;
+#pragma unroll
+    for (int j = 0; j < IPT; ++j) {
+      if (i0 + j < V) {
+        float x = raw[j];
+        if ((pres >> j) & 1u) x = x < 0.f ? x * penalty : x / penalty;
+        float z;
+        {
+#pragma clang fp contract(off)  // z is the rounded product wherever it is used: equal keys share bins and masses
+          z = x * inv_temp;
+        }
+        fn(i0 + j, x, z);
+      }
+    }
+  }
+}
+
+struct Shared {
+  u64 hist[BINS];
+  u64 wsum[NT / 64];
+  float redf[NT / 64];
+  int redi[NT / 64];
+  int bin;   // the select's chosen bin
+  u64 rest;  // and the threshold left inside it
+};
+
+// The edge of one cut: the largest key e such that the tokens with key >= e (among those with key >= floor_key) are
+// the kept set. Counting (MASS false): ``thr`` = k - 1. Mass (MASS true): the threshold is floor(top_p S).
+template <typename T, bool MASS>
+__device__ __forceinline__ unsigned select_edge(Shared& sh, const T* __restrict__ row, int V,
+                                                const unsigned* __restrict__ pres_row, float inv_temp, float penalty,
+                                                float m, unsigned floor_key, u64 thr, double top_p) {
+  const int t = threadIdx.x;
+  int b1 = 0;
+  unsigned pfx = 0;
+  for (int lvl = 0; lvl < 4; ++lvl) {
+    sh.hist[2 * t] = 0;
+    sh.hist[2 * t + 1] = 0;
+    if (t == 0) {
+      sh.bin = BINS - 1;
+      sh.rest = 0;
+    }
+    __syncthreads();
+    sweep<T>(row, V, pres_row, inv_temp, penalty, [&](int, float, float z) {
+      const unsigned key = okey(z);
+      if (key < floor_key) return;
+      int bin = lin_bin(m, z);
+      if (lvl > 0) {
+        if (bin != b1) return;
+        if (lvl == 1) {
+          bin = BINS - 1 - (int)(key >> 21);
+        } else if (lvl == 2) {
+          if ((key >> 21) != pfx) return;
+          bin = BINS - 1 - (int)((key >> 10) & 2047u);
+        } else {
+          if ((key >> 10) != pfx) return;
+          bin = 1023 - (int)(key & 1023u);
+        }
+      }
+      const u64 w = MASS ? mass_of(m, z) : 1ull;
+      if (w) atomicAdd(&sh.hist[bin], w);
+    });
+    __syncthreads();
+    // inclusive scan over the bins, two per thread: within the wave by shuffles, across the 16 waves through LDS
+    const u64 a = sh.hist[2 * t], b = sh.hist[2 * t + 1];
+    u64 incl = a + b;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned lo = __shfl_up((unsigned)incl, o, 64), hi = __shfl_up((unsigned)(incl >> 32), o, 64);
+      if ((t & 63) >= o) incl += ((u64)hi << 32) | lo;
+    }
+    if ((t & 63) == 63) sh.wsum[t >> 6] = incl;
+    __syncthreads();
+    u64 off = 0, total = 0;
+    for (int w = 0; w < NT / 64; ++w) {
+      if (w < (t >> 6)) off += sh.wsum[w];
+      total += sh.wsum[w];
+    }
+    if (MASS && lvl == 0) {
+      if (total == 0) return floor_key;  // (a row of NaNs or infinities has no mass: no nucleus cut)
+      thr = (u64)(top_p * (double)total);
+      if (thr >= total) thr = total - 1;
+    }
+    const u64 ex = off + incl - (a + b);  // what lies above bin 2t
+    if (a && ex <= thr && thr < ex + a) {
+      sh.bin = 2 * t;
+      sh.rest = thr - ex;
+    } else if (b && ex + a <= thr && thr < ex + a + b) {
+      sh.bin = 2 * t + 1;
+      sh.rest = thr - ex - a;
+    }
+    __syncthreads();
+    const int bin = sh.bin;
+    thr = sh.rest;
+    if (lvl == 0) b1 = bin;
+    else if (lvl == 1) pfx = (unsigned)(BINS - 1 - bin);
+    else if (lvl == 2) pfx = (pfx << 11) | (unsigned)(BINS - 1 - bin);
+    else pfx = (pfx << 10) | (unsigned)(1023 - bin);
+    __syncthreads();  // sh.bin / sh.rest are reset by the next level
+  }
+  return pfx;
+}
+
+// grid B (1 for sample_token, with ``done`` null): the whole draw of row b, which uses seed + b.
+template <typename T>
+__global__ __launch_bounds__(NT) void select_kernel(const T* __restrict__ logits, int V,
+                                                    unsigned* __restrict__ presence, int words, float inv_temp,
+                                                    float penalty, int K, double top_p, unsigned seed,
+                                                    long long* __restrict__ state, long long* __restrict__ tok_out,
+                                                    long long* __restrict__ pos_out, int* __restrict__ len_out,
+                                                    long long* __restrict__ log, int log_cap, int* __restrict__ done,
+                                                    int eos) {
+  __shared__ Shared sh;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (done && done[b]) return;
+  const T* row = logits + (long)b * V;
+  unsigned* pres_row = presence + (long)b * words;
+  long long* st = state + (long)b * 4;
+  const long long step = st[0];
+  const unsigned sd = seed + (unsigned)b;
+  const bool nucleus = top_p < 1.0;
+
+  unsigned edge = 0;
+  if (K > 0 || nucleus) {
+    float m = -INFINITY;
+    sweep<T>(row, V, pres_row, inv_temp, penalty, [&](int, float, float z) { m = fmaxf(m, z); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((t & 63) == 0) sh.redf[t >> 6] = m;
+    __syncthreads();
+    for (int w = 0; w < NT / 64; ++w) m = fmaxf(m, sh.redf[w]);
+    __syncthreads();
+    if (K > 0) edge = select_edge<T, false>(sh, row, V, pres_row, inv_temp, penalty, m, 0u, (u64)(K - 1), 0.0);
+    if (nucleus) edge = select_edge<T, true>(sh, row, V, pres_row, inv_temp, penalty, m, edge, 0ull, top_p);
+  }
+
+  // Gumbel arg-max over the kept set: full_partial_kernel's key (which the compiler contracts there to one fma of
+  // the penalised logit, 1 / temperature and the Gumbel term; here it is written out), full_merge's order
+  float best = -INFINITY;
+  int best_i = 0x7fffffff;
+  sweep<T>(row, V, pres_row, inv_temp, penalty, [&](int i, float x, float z) {
+    if (okey(z) < edge) return;
+    const unsigned h = hash_u32(((unsigned long long)step << 32) | (unsigned long long)(unsigned)i, sd);
+    const float u = ((float)(h >> 9) + 0.5f) * (1.f / 8388608.f);
+    const float key = __builtin_fmaf(x, inv_temp, 0.f - logf(0.f - logf(u)));
+    if (key > best || (key == best && i < best_i)) {
+      best = key;
+      best_i = i;
+    }
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float k2 = __shfl_xor(best, o, 64);
+    const int i2 = __shfl_xor(best_i, o, 64);
+    if (k2 > best || (k2 == best && i2 < best_i)) {
+      best = k2;
+      best_i = i2;
+    }
+  }
+  if ((t & 63) == 0) {
+    sh.redf[t >> 6] = best;
+    sh.redi[t >> 6] = best_i;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  for (int w = 1; w < NT / 64; ++w) {
+    const float k2 = sh.redf[w];
+    const int i2 = sh.redi[w];
+    if (k2 > best || (k2 == best && i2 < best_i)) {
+      best = k2;
+      best_i = i2;
+    }
+  }
+  int tok = best_i;
+  if (tok < 0 || tok >= V) tok = 0;  // (a row of NaNs has no best key)
+  commit_token(tok, step, st, tok_out ? tok_out + b : nullptr, pos_out ? pos_out + b : nullptr,
+               len_out ? len_out + b : nullptr, log ? log + (long)b * log_cap : nullptr, log_cap, pres_row,
+               done ? done + b : nullptr, eos);
+}
+
+template <typename T>
+void launch_select(const at::Tensor& logits, int B, int V, at::Tensor& presence, int words, double temperature,
+                   double repetition_penalty, int K, double top_p, int64_t seed, at::Tensor& state,
+                   const c10::optional<at::Tensor>& tok_out, const c10::optional<at::Tensor>& pos_out,
+                   const c10::optional<at::Tensor>& len_out, const c10::optional<at::Tensor>& log, int log_cap,
+                   int* done, int eos) {
+  SFT_TRACE("samp.select");
+  select_kernel<T><<<B, NT, 0, cur_stream()>>>(
+      (const T*)logits.data_ptr(), V, (unsigned*)presence.data_ptr<int>(), words,
+      (float)(1.0 / std::max(temperature, 1e-5)), (float)repetition_penalty, K, top_p, (unsigned)seed,
+      (long long*)state.data_ptr<int64_t>(), tok_out.has_value() ? (long long*)tok_out->data_ptr<int64_t>() : nullptr,
+      pos_out.has_value() ? (long long*)pos_out->data_ptr<int64_t>() : nullptr,
+      len_out.has_value() ? len_out->data_ptr<int>() : nullptr,
+      log.has_value() ? (long long*)log->data_ptr<int64_t>() : nullptr, log_cap, done, eos);
+  SFT_LAUNCH_CHECK();
+}
+
+}  // namespace sel
 }  // namespace samp
 
 // logits [V] (bf16 or fp32). presence int32 bitmask [ceil(V/32)]. state int64 [4]. tok_out / pos_out int64 [1]
-// and len_out int32 [1] are optional (the decode graph's inputs). log int64 [cap] optional.
+// and len_out int32 [1] are optional (the decode graph's inputs). log int64 [cap] optional. top_k in [1, 64] runs the
+// tile sort, 0 (no top-k cut) and 65 .. V the threshold sampler; above V it is refused.
 void sample_token(const at::Tensor& logits, at::Tensor presence, at::Tensor state, const c10::optional<at::Tensor>& tok_out,
                   const c10::optional<at::Tensor>& pos_out, const c10::optional<at::Tensor>& len_out,
                   const c10::optional<at::Tensor>& log, double temperature, int64_t top_k, double top_p,
@@ -373,12 +646,24 @@ void sample_token(const at::Tensor& logits, at::Tensor presence, at::Tensor stat
   SFT_CHECK(presence.scalar_type() == at::kInt && presence.numel() >= (V + 31) / 32 && presence.is_contiguous(),
             "sample_token: presence int32 bitmask");
   SFT_CHECK(state.scalar_type() == at::kLong && state.numel() >= 4, "sample_token: state int64[4]");
+  SFT_CHECK(!do_sample || (top_k >= 0 && top_k <= V), "sample_token: top_k must be in [0, V] (0: no top-k cut)");
   const int K = do_sample ? (int)top_k : 1;
-  SFT_CHECK(K >= 1 && K <= samp::KMAX && K <= V, "sample_token: top_k must be in [1, min(64, V)] on the device path");
-  const int nblk = (V + samp::TILE - 1) / samp::TILE;
-  SFT_CHECK(nblk * K <= samp::NT * samp::IPT2, "sample_token: vocabulary too large for one merge block");
   SFT_CHECK(!pos_out.has_value() || (len_out.has_value() && pos_out->scalar_type() == at::kLong &&
                                      len_out->scalar_type() == at::kInt), "sample_token: pos int64 / len int32");
+  if (K == 0 || K > samp::KMAX) {  // the threshold sampler: one workgroup, no workspace
+    SFT_CHECK(logits.numel() < (1L << 31) - samp::TILE, "sample_token: vocabulary");
+    const int cap = log.has_value() ? (int)log->numel() : 0;
+    if (logits.scalar_type() == at::kFloat)
+      samp::sel::launch_select<float>(logits, 1, V, presence, 0, temperature, repetition_penalty, K, top_p, seed, state,
+                                      tok_out, pos_out, len_out, log, cap, nullptr, -1);
+    else
+      samp::sel::launch_select<u16>(logits, 1, V, presence, 0, temperature, repetition_penalty, K, top_p, seed, state,
+                                    tok_out, pos_out, len_out, log, cap, nullptr, -1);
+    return;
+  }
+  SFT_CHECK(K <= V, "sample_token: top_k must be in [1, V]");
+  const int nblk = (V + samp::TILE - 1) / samp::TILE;
+  SFT_CHECK(nblk * K <= samp::NT * samp::IPT2, "sample_token: vocabulary too large for one merge block");
   auto cv = at::empty({nblk * K}, logits.options().dtype(at::kFloat));
   auto ci = at::empty({nblk * K}, logits.options().dtype(at::kInt));
   const float inv_t = do_sample ? (float)(1.0 / std::max(temperature, 1e-5)) : 1.f;
@@ -423,10 +708,12 @@ void sample_tokens(const at::Tensor& logits, at::Tensor presence, at::Tensor sta
                 state.size(1) == 4 && state.is_contiguous(), "sample_tokens: state int64 [B, 4]");
   SFT_CHECK(done.is_cuda() && done.scalar_type() == at::kInt && done.numel() == B && done.is_contiguous(),
             "sample_tokens: done int32 [B]");
+  SFT_CHECK(!do_sample || (top_k >= 0 && top_k <= V), "sample_tokens: top_k must be in [0, V] (0: no top-k cut)");
   const int K = do_sample ? (int)top_k : 1;
-  SFT_CHECK(K >= 1 && K <= samp::KMAX && K <= V, "sample_tokens: top_k must be in [1, min(64, V)] on the device path");
+  const bool select = K == 0 || K > samp::KMAX;  // the threshold sampler
   const int nblk = (V + samp::TILE - 1) / samp::TILE;
-  SFT_CHECK(nblk * K <= samp::NT * samp::IPT2, "sample_tokens: vocabulary too large for one merge block");
+  SFT_CHECK(select || nblk * K <= samp::NT * samp::IPT2, "sample_tokens: vocabulary too large for one merge block");
+  SFT_CHECK(!select || logits.size(1) < (1L << 31) - samp::TILE, "sample_tokens: vocabulary");
   SFT_CHECK(!tok_out.has_value() || (tok_out->is_cuda() && tok_out->scalar_type() == at::kLong &&
                                      tok_out->numel() == B && tok_out->is_contiguous()), "sample_tokens: tok int64 [B]");
   SFT_CHECK(!pos_out.has_value() ||
@@ -435,6 +722,18 @@ void sample_tokens(const at::Tensor& logits, at::Tensor presence, at::Tensor sta
                  pos_out->is_contiguous() && len_out->is_contiguous()), "sample_tokens: pos int64 [B] / len int32 [B]");
   SFT_CHECK(!log.has_value() || (log->is_cuda() && log->scalar_type() == at::kLong && log->dim() == 2 &&
                                  log->size(0) == B && log->is_contiguous()), "sample_tokens: log int64 [B, cap]");
+  if (select) {  // one workgroup per row, no workspace
+    const int cap = log.has_value() ? (int)log->size(1) : 0;
+    if (logits.scalar_type() == at::kFloat)
+      samp::sel::launch_select<float>(logits, (int)B, V, presence, (int)presence.size(1), temperature,
+                                      repetition_penalty, K, top_p, seed, state, tok_out, pos_out, len_out, log, cap,
+                                      done.data_ptr<int>(), (int)eos_token_id);
+    else
+      samp::sel::launch_select<u16>(logits, (int)B, V, presence, (int)presence.size(1), temperature,
+                                    repetition_penalty, K, top_p, seed, state, tok_out, pos_out, len_out, log, cap,
+                                    done.data_ptr<int>(), (int)eos_token_id);
+    return;
+  }
   auto cv = at::empty({B * nblk * K}, logits.options().dtype(at::kFloat));
   auto ci = at::empty({B * nblk * K}, logits.options().dtype(at::kInt));
   const float inv_t = do_sample ? (float)(1.0 / std::max(temperature, 1e-5)) : 1.f;

@@ -165,9 +165,11 @@ def _presence(vocab_size: int, histories, device) -> torch.Tensor:
     return torch.from_numpy(words.view(np.int32).copy()).to(device)
 
 
-def _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed):
-    """The scalar arguments of the two sampler ops, in their order. Greedy is top-1; no seed draws one."""
-    return (float(temperature), int(top_k) if do_sample else 1, float(top_p if top_p is not None else 1.0),
+def _sampler_params(vocab_size, temperature, top_k, top_p, repetition_penalty, do_sample, seed):
+    """The scalar arguments of the two sampler ops, in their order. Greedy is top-1; ``top_k`` 0 or None is no top-k
+    cut, and a ``top_k`` above the vocabulary is clamped to it (as HF does); no seed draws one."""
+    return (float(temperature), min(int(top_k or 0), vocab_size) if do_sample else 1,
+            float(top_p if top_p is not None else 1.0),
             float(repetition_penalty or 1.0), bool(do_sample),
             int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()))
 
@@ -175,18 +177,22 @@ def _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, se
 class DeviceSampler:
     """GPU-resident sampling state of one sequence for the fused HIP sampler (csrc/sampler.hip): the
     history as a presence bitmask (repetition penalty is a set operation), a step counter that keys the
-    counter-based RNG, the running position / KV length, and a device log of the generated tokens."""
+    counter-based RNG, the running position / KV length, and a device log of the generated tokens.
+
+    ``1 <= top_k <= 64`` runs the tile-sort kernels; ``top_k == 0`` (nucleus alone, or no cut) and ``top_k > 64`` run
+    the threshold sampler (radix select of the cut values, Gumbel-max draw over the kept set). Either way a seed
+    yields other tokens than the host loop's ``multinomial`` draws from it."""
 
     def __init__(self, vocab_size: int, device, history_ids, max_new_tokens: int, seed: Optional[int],
                  temperature: float, top_k: int, top_p: Optional[float], repetition_penalty: float, do_sample: bool):
         self.presence = _presence(vocab_size, [history_ids], device)[0]
         self.state = torch.zeros(4, dtype=torch.long, device=device)
         self.log = torch.full((max(1, max_new_tokens),), -1, dtype=torch.long, device=device)
-        self.params = _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed)
+        self.params = _sampler_params(vocab_size, temperature, top_k, top_p, repetition_penalty, do_sample, seed)
 
     @staticmethod
-    def supported(top_k: int, do_sample: bool) -> bool:
-        return (not do_sample) or (top_k is not None and 1 <= top_k <= 64)
+    def supported(top_k: Optional[int], do_sample: bool) -> bool:
+        return (not do_sample) or int(top_k or 0) >= 0
 
     def sample(self, logits: torch.Tensor, tok_out=None, pos_out=None, len_out=None) -> None:
         t, k, p, rp, ds, seed = self.params
@@ -277,6 +283,9 @@ def generate(model, prompt_ids: List[int], max_new_tokens: int = 256, eos_token_
              temperature: float = 0.6, top_k: int = 40, top_p: float = 0.95, repetition_penalty: float = 1.1,
              do_sample: bool = True, seed: Optional[int] = None, use_graph: Optional[bool] = None,
              device_sampling: Optional[bool] = None) -> List[int]:
+    """One prompt's completion. On the HIP path the decode step and the sampler run in one captured graph for every
+    sampling setting (``top_k`` 0 or None: no top-k cut; above the vocabulary: clamped); ``device_sampling=False``
+    gives the host loop, whose ``multinomial`` draws other tokens from the same seed."""
     model.eval()
     dev = model.model.embed_tokens.device
     cache = KVCache(model.config, len(prompt_ids) + max_new_tokens + 1, dev, model.model.embed_tokens.dtype)
@@ -388,7 +397,7 @@ class BatchDeviceSampler:
         self.log = torch.full((B, max(1, max_new_tokens)), -1, dtype=torch.long, device=device)
         self.done = torch.zeros(B, dtype=torch.int32, device=device)
         self.eos = -1 if eos_token_id is None else int(eos_token_id)
-        self.params = _sampler_params(temperature, top_k, top_p, repetition_penalty, do_sample, seed)
+        self.params = _sampler_params(vocab_size, temperature, top_k, top_p, repetition_penalty, do_sample, seed)
 
     def sample(self, logits: torch.Tensor, tok_out=None, pos_out=None, len_out=None) -> None:
         t, k, p, rp, ds, seed = self.params
@@ -486,7 +495,9 @@ def generate_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, e
                    device_sampling: Optional[bool] = None) -> List[List[int]]:
     """Element b is what ``generate(model, prompts[b], ..., seed=seed + b)`` returns: every sequence stops at its
     own EOS (included) or at ``max_new_tokens``. All prompts are prefilled in one packed pass and decoded one
-    token per sequence and step, so the weights are read once per step for the whole batch."""
+    token per sequence and step, so the weights are read once per step for the whole batch. On the HIP path every
+    sampling setting runs on the device by default (``top_k`` 0 or None: no top-k cut; above the vocabulary: clamped);
+    ``device_sampling=False`` gives the host loop, whose ``multinomial`` draws other tokens from the same seed."""
     model.eval()
     B = len(prompts)
     if B == 0:
@@ -565,8 +576,9 @@ def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eo
     its EOS (included) or at ``max_new_tokens``. With ``top_k == 0`` every token is a draw from softmax(penalised
     logits / temperature) over the WHOLE vocabulary and ``logps[b][i]`` is its log-probability under that distribution;
     on the HIP path the batched graph decoder runs with ``sample_tokens_full`` inside the captured step, off it (or with
-    ``device_sampling=False``) the host loop draws with ``multinomial``. With ``1 <= top_k <= 64`` the existing device
-    sampler draws from the top k and ``logps`` is None (a truncated behaviour policy has no full-vocabulary ratio).
+    ``device_sampling=False``) the host loop draws with ``multinomial``. With ``top_k >= 1`` (clamped to the vocabulary)
+    the device sampler draws from the top k (above 64: the threshold sampler, whose tokens for a seed are not the host
+    loop's) and ``logps`` is None (a truncated behaviour policy has no full-vocabulary ratio).
     The model's ``training`` flag is restored on return."""
     was_training = model.training
     model.eval()

@@ -11,6 +11,7 @@ child builds the model, warms the timed shape up once (kernels, library algorith
 reports a host-clock time around a call that ends in a device-to-host read of the tokens.
 
     python tools/bench_generate.py --arm batch --batch 16          # one arm, one JSON line (what the children run)
+    python tools/bench_generate.py --arm batch --batch 16 --top-k 0 --top-p 0.9 [--host-sampling]   # sampled decoding
     rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/bench_generate.py --arm batch --batch 16
     python tools/bench_generate.py --kernel-split DIR/.../*_kernel_trace.csv   # GEMMs / attention / sampler per step
 """
@@ -29,7 +30,8 @@ if ROOT not in sys.path:
 PROMPT, NEW = 128, 128
 
 
-def run_arm(arm: str, B: int, reps: int, model_name: str = "smollm3-3b") -> dict:
+def run_arm(arm: str, B: int, reps: int, model_name: str = "smollm3-3b", top_k=None, top_p=None,
+            host_sampling: bool = False) -> dict:
     import torch
     from llm_fine_tune_distributed_amd.inference.generation import generate, generate_batch
     from llm_fine_tune_distributed_amd.models import build_model, get_config
@@ -41,6 +43,10 @@ def run_arm(arm: str, B: int, reps: int, model_name: str = "smollm3-3b") -> dict
     g = torch.Generator().manual_seed(1)
     prompts = [torch.randint(0, cfg.vocab_size, (PROMPT,), generator=g).tolist() for _ in range(B)]
     kw = dict(max_new_tokens=NEW, do_sample=False, repetition_penalty=1.0, eos_token_id=None)
+    if top_k is not None or top_p is not None:  # sampled decoding with these cuts instead of greedy
+        kw.update(do_sample=True, top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, seed=0)
+        if host_sampling:
+            kw.update(device_sampling=False)
 
     def once():
         if arm == "seq":
@@ -59,7 +65,8 @@ def run_arm(arm: str, B: int, reps: int, model_name: str = "smollm3-3b") -> dict
         times.append(time.perf_counter() - t0)
     best = min(times)
     return {"arm": arm, "batch": B, "new_tokens": B * NEW, "seconds": times, "tokens_per_s": B * NEW / best,
-            "device": torch.cuda.get_device_name(0), "layers": cfg.num_hidden_layers, "model": model_name}
+            "device": torch.cuda.get_device_name(0), "layers": cfg.num_hidden_layers, "model": model_name,
+            "top_k": top_k, "top_p": top_p, "host_sampling": host_sampling}
 
 
 def kernel_split(path: str) -> str:
@@ -70,7 +77,7 @@ def kernel_split(path: str) -> str:
         for r in csv.DictReader(f):
             rows.append((r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     rows.sort(key=lambda r: r[1])
-    marks = [i for i, r in enumerate(rows) if "final_batched_kernel" in r[0]]
+    marks = [i for i, r in enumerate(rows) if "final_batched_kernel" in r[0] or "select_kernel" in r[0]]
     assert len(marks) > NEW, "no batched decode steps in this trace"
     # the last NEW - 1 steps are the timed call's decode steps (the first token comes from the prefill logits)
     lo, hi = marks[-NEW], marks[-1]
@@ -109,6 +116,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions per arm (best is reported)")
     ap.add_argument("--arm-timeout", type=int, default=300, help="seconds each arm's child may take")
+    ap.add_argument("--top-k", type=int, help="with --arm: sample with this top-k cut (0: none) instead of greedy")
+    ap.add_argument("--top-p", type=float, help="with --arm: sample with this nucleus cut instead of greedy")
+    ap.add_argument("--host-sampling", action="store_true", help="with --arm: sample in the host loop, not on the device")
     ap.add_argument("--out", help="write the table as markdown")
     ap.add_argument("--kernel-split", metavar="KERNEL_TRACE_CSV")
     a = ap.parse_args(argv)
@@ -116,7 +126,7 @@ def main(argv=None):
         print(kernel_split(a.kernel_split))
         return
     if a.arm:
-        print(json.dumps(run_arm(a.arm, a.batch, a.reps, a.model)))
+        print(json.dumps(run_arm(a.arm, a.batch, a.reps, a.model, a.top_k, a.top_p, a.host_sampling)))
         return
     results = {}
     for B in a.batches:
