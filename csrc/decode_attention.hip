@@ -266,8 +266,82 @@ at::Tensor decode_attention(const at::Tensor& q, const at::Tensor& kcache, const
 // One decode step of B sequences: append row b's K/V at cache[b, lens[b] - 1], then attend over cache[b, :lens[b]].
 // qkv [B, (nq + 2 nkv) * D] (post-RoPE), kcache / vcache [B, S_max, nkv, D] with D = 64 or 128, lens int32 [B] on the
 // device (live length INCLUDING the token being decoded). Static shapes, no host sync: lives inside a captured graph.
+//
+// With a prefix (all of prefix_k / prefix_v [n_groups, P_max, nkv, D], prefix_lens int32 [n_groups] on the device, and
+// group = G with B == n_groups * G): row b belongs to group b / G, the caches hold only the rows' own tokens, and
+// lens[b] still counts everything: own = lens[b] - prefix_lens[b / G] (prefix_lens clamped to [0, P_max]). The append
+// goes to own row own - 1 and row b attends over prefix[b / G, :prefix_lens] plus cache[b, :own]; a row whose own is
+// outside (0, S_own] is skipped and attends over its prefix alone. MFMA kernels at head_dim 64 and 128
+// (csrc/decode_attention_d64.hip), no sliding window.
+static at::Tensor decode_attention_prefixed(const at::Tensor& qkv, at::Tensor& kcache, at::Tensor& vcache,
+                                            const at::Tensor& lens, int64_t nq, int64_t nkv, double scale,
+                                            int64_t window, const at::Tensor& pk, const at::Tensor& pv,
+                                            const at::Tensor& plens, int64_t group) {
+  const char* op = "decode_attention_batched";
+  SFT_CHECK(window == 0, op, ": no sliding window together with a prefix");
+  SFT_CHECK(qkv.is_cuda() && kcache.is_cuda() && vcache.is_cuda() && pk.is_cuda() && pv.is_cuda(), op,
+            ": GPU tensors");
+  SFT_CHECK(qkv.scalar_type() == at::kBFloat16 && kcache.scalar_type() == at::kBFloat16 &&
+                vcache.scalar_type() == at::kBFloat16,
+            op, ": qkv and the caches must be bfloat16");
+  SFT_CHECK(pk.scalar_type() == at::kBFloat16 && pv.scalar_type() == at::kBFloat16, op,
+            ": the prefix must be bfloat16 like the cache");
+  SFT_CHECK(qkv.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous() && pk.is_contiguous() &&
+                pv.is_contiguous(),
+            op, ": qkv, the caches and the prefix must be contiguous");
+  SFT_CHECK(nq > 0 && nkv > 0 && nq % nkv == 0 && nq / nkv <= decode::MAXREP, op, ": GQA ratio <= 8");
+  SFT_CHECK(kcache.dim() == 4 && pk.dim() == 4, op, ": kcache [B, S, nkv, head_dim], prefix [n, P, nkv, head_dim]");
+  const int64_t hd = cache_head_dim(op, kcache, 0);
+  SFT_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * hd, op, ": qkv must be [B, (nq + 2 nkv) * head_dim]");
+  const int64_t B = qkv.size(0);
+  SFT_CHECK(kcache.size(0) == B && kcache.size(2) == nkv && vcache.sizes() == kcache.sizes(), op,
+            ": kcache / vcache [B, S, nkv, head_dim]");
+  SFT_CHECK(group >= 1 && B >= 1 && B % group == 0, op, ": B = ", B, " is no multiple of group = ", group);
+  const int64_t ng = B / group;
+  SFT_CHECK(pk.size(0) == ng && pv.sizes() == pk.sizes(), op, ": prefix_k / prefix_v [B / group, P, nkv, head_dim]");
+  SFT_CHECK(pk.size(2) == nkv && pk.size(3) == hd, op, ": the prefix has ", pk.size(2), " kv heads of head_dim ",
+            pk.size(3), ", the cache ", nkv, " of ", hd);
+  SFT_CHECK(lens.scalar_type() == at::kInt && lens.is_cuda() && lens.is_contiguous() && lens.numel() == B, op,
+            ": lens int32 [B] on device");
+  SFT_CHECK(plens.scalar_type() == at::kInt && plens.is_cuda() && plens.is_contiguous() && plens.numel() == ng, op,
+            ": prefix_lens int32 [B / group] on device");
+  SFT_CHECK(B <= 65535 && nkv <= 65535, op, ": batch size");
+  SFT_CHECK(aligned16(qkv) && aligned16(kcache) && aligned16(vcache) && aligned16(pk) && aligned16(pv), op,
+            ": 16-byte aligned");
+  const int64_t sown = kcache.size(1), pmax = pk.size(1);
+  SFT_CHECK(sown >= 1 && pmax >= 1 && sown + pmax < (1 << 30), op, ": empty cache or prefix");
+  const int64_t splits = (pmax + decode::CHUNK - 1) / decode::CHUNK + (sown + decode::CHUNK - 1) / decode::CHUNK;
+  const int64_t rep = nq / nkv;
+  auto po = at::empty({B * nkv * splits * rep * hd}, qkv.options().dtype(at::kFloat));
+  auto pml = at::empty({B * nkv * splits * rep * 2}, qkv.options().dtype(at::kFloat));
+  auto out = at::empty({B, nq * hd}, qkv.options());
+  SFT_TRACE("decode.prefix");
+  decode64::launch_prefix_step(hd, (const u16*)qkv.data_ptr(), (u16*)kcache.data_ptr(), (u16*)vcache.data_ptr(),
+                               lens.data_ptr<int>(), (const u16*)pk.data_ptr(), (const u16*)pv.data_ptr(),
+                               plens.data_ptr<int>(), po.data_ptr<float>(), pml.data_ptr<float>(), B, group, nq, nkv,
+                               sown, pmax, (float)scale * decode::LOG2E, cur_stream());
+  if (hd == decode64::D)
+    decode::combine_batched_kernel<decode64::D><<<dim3(nq, B), decode64::D, 0, cur_stream()>>>(
+        po.data_ptr<float>(), pml.data_ptr<float>(), (u16*)out.data_ptr(), nq, nkv, splits);
+  else
+    decode::combine_batched_kernel<decode::D><<<dim3(nq, B), decode::D, 0, cur_stream()>>>(
+        po.data_ptr<float>(), pml.data_ptr<float>(), (u16*)out.data_ptr(), nq, nkv, splits);
+  SFT_LAUNCH_CHECK();
+  return out;
+}
+
 at::Tensor decode_attention_batched(const at::Tensor& qkv, at::Tensor kcache, at::Tensor vcache, const at::Tensor& lens,
-                                    int64_t nq, int64_t nkv, double scale, int64_t window) {
+                                    int64_t nq, int64_t nkv, double scale, int64_t window,
+                                    const c10::optional<at::Tensor>& prefix_k,
+                                    const c10::optional<at::Tensor>& prefix_v,
+                                    const c10::optional<at::Tensor>& prefix_lens, int64_t group) {
+  if (prefix_k.has_value() || prefix_v.has_value() || prefix_lens.has_value()) {
+    SFT_CHECK(prefix_k.has_value() && prefix_v.has_value() && prefix_lens.has_value(),
+              "decode_attention_batched: prefix_k, prefix_v and prefix_lens go together");
+    return decode_attention_prefixed(qkv, kcache, vcache, lens, nq, nkv, scale, window, *prefix_k, *prefix_v,
+                                     *prefix_lens, group);
+  }
+  SFT_CHECK(group == 1, "decode_attention_batched: group = ", group, " needs a prefix");
   SFT_CHECK_CUDA(qkv);
   SFT_CHECK_BF16(qkv);
   SFT_CHECK_BF16(kcache);

@@ -20,5 +20,15 @@ void launch_split(const u16* q, const u16* kc, const u16* vc, const int* len_p, 
 void launch_split_batched(const u16* qkv, const u16* kc, const u16* vc, const int* lens, float* part_o, float* part_ml,
                           int B, int nq, int nkv, int smax, float sl2, hipStream_t st);
 
+// Shared-prefix step of B = n_groups * G rows at head_dim hd (64 or 128), csrc/decode_attention_d64.hip: row b attends
+// over prefix[b / G, :plens[b / G]] (pk / pv [n_groups, pmax, nkv, hd], plens [n_groups] int32, clamped to [0, pmax])
+// and over its own slab kc / vc [B, sown, nkv, hd], whose live length is own = lens[b] - plens[b / G]. The append
+// stores the step's K/V at own row own - 1 (own outside (0, sown]: the row is skipped and attends over its prefix
+// alone). part_o [B, nkv, splits_total, rep, hd] / part_ml [.., 2] with splits_total = ceil(pmax / 256) +
+// ceil(sown / 256): the prefix kernel fills the first ceil(pmax / 256) slots of every row, the suffix kernel the rest.
+void launch_prefix_step(int hd, const u16* qkv, u16* kc, u16* vc, const int* lens, const u16* pk, const u16* pv,
+                        const int* plens, float* part_o, float* part_ml, int B, int G, int nq, int nkv, int sown,
+                        int pmax, float sl2, hipStream_t st);
+
 }  // namespace decode64
 }  // namespace sftamd

@@ -355,16 +355,56 @@ class BatchKVCache:
         self.v = torch.empty_like(self.k)
         self.lens = [0] * batch
 
+    group = 1                  # rows per shared prefix (GroupedKVCache)
+    pk = pv = plens = None     # the shared prefixes' K/V and lengths: none here
+
+
+class GroupedKVCache(BatchKVCache):
+    """BatchKVCache of ``n_prompts * group`` rows, prompt-major, whose ``group`` rows of a prompt share its K/V:
+    ``pk[li]`` / ``pv[li]`` [n_prompts, P_max, nkv, D] hold every prompt once (written by ``prefill_grouped``, with the
+    lengths in ``plens``, int32 on the device), ``k[li]`` / ``v[li]`` [B, own_len, nkv, D] only what a row generates.
+    ``lens[b]`` still counts row b's prompt and generated tokens. The prompt part of the cache is ``group`` times
+    smaller than BatchKVCache's, and the decode step reads it once per group (``ops.decode_attention_batched`` with a
+    prefix)."""
+
+    def __init__(self, cfg, n_prompts: int, group: int, prefix_len: int, own_len: int, device, dtype=torch.bfloat16):
+        super().__init__(cfg, n_prompts * group, own_len, device, dtype)
+        self.group = int(group)
+        self.pk = torch.empty(cfg.num_hidden_layers, n_prompts, prefix_len, cfg.num_key_value_heads, cfg.head_dim,
+                              device=device, dtype=dtype)
+        self.pv = torch.empty_like(self.pk)
+        self.plens = torch.zeros(n_prompts, dtype=torch.int32, device=device)
+
 
 @torch.no_grad()
 def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch.Tensor:
     """All prompts in ONE packed varlen pass (cu_seqlens, per-sample positions) through the ops forward_cached
     uses; K/V are scattered into each sequence's slab. Returns the last-token logits [B, V] (fp32)."""
+    assert len(prompts) == len(cache.lens), "prompts do not fit the cache"
+    logits = _prefill_into(model, prompts, cache.k, cache.v)
+    cache.lens = [len(p) for p in prompts]
+    return logits
+
+
+@torch.no_grad()
+def prefill_grouped(model, prompts: List[List[int]], cache: GroupedKVCache) -> torch.Tensor:
+    """``prefill_batch`` over the UNIQUE prompts of a GroupedKVCache: one packed pass, K/V scattered into the prefix
+    slabs. Returns the last-token logits repeated for every row of a group, [n_prompts * group, V]."""
+    assert len(prompts) == cache.pk.shape[1], "prompts do not fit the cache"
+    logits = _prefill_into(model, prompts, cache.pk, cache.pv)
+    n = [len(p) for p in prompts]
+    cache.plens.copy_(torch.tensor(n, dtype=torch.int32))
+    cache.lens = [x for x in n for _ in range(cache.group)]
+    return logits.repeat_interleave(cache.group, 0)
+
+
+def _prefill_into(model, prompts: List[List[int]], kdst: torch.Tensor, vdst: torch.Tensor) -> torch.Tensor:
+    """The packed prefill pass; sequence b's K/V of layer li go to ``kdst[li, b, :len(prompts[b])]`` (and vdst)."""
     dev = model.model.embed_tokens.device
     nq, nkv, D = _heads(model.config)
     W = _windows(model)
     n = [len(p) for p in prompts]
-    assert len(n) == len(cache.lens) and min(n) > 0 and max(n) <= cache.k.shape[2], "prompts do not fit the cache"
+    assert min(n) > 0 and max(n) <= kdst.shape[2], "prompts do not fit the cache"
     ids = torch.tensor([t for p in prompts for t in p], device=dev)
     bounds = [0]
     for x in n:
@@ -374,11 +414,10 @@ def prefill_batch(model, prompts: List[List[int]], cache: BatchKVCache) -> torch
     seq = torch.repeat_interleave(torch.arange(len(n)), torch.tensor(n)).to(dev)
 
     def attend(li, qkv):
-        cache.k[li][seq, pos], cache.v[li][seq, pos] = _kv_rows(model.config, qkv)
+        kdst[li][seq, pos], vdst[li][seq, pos] = _kv_rows(model.config, qkv)
         return ops.flash_attention(qkv.contiguous(), cu, max(n), nq, nkv, D, window=W[li])
 
     x, residual = _run_layers(model, ids, pos, attend)
-    cache.lens = list(n)
     last = (cu[1:] - 1).long()
     return _logits(model, x[last], residual[last])
 
@@ -432,7 +471,8 @@ class FullVocabSampler(BatchDeviceSampler):
 class BatchGraphDecoder:
     """GraphDecoder for B sequences over a BatchKVCache: the step runs M = B rows through the same ops, with the
     batched HIP decode attention (csrc/decode_attention.hip) appending each row's K/V and attending over its own
-    slab. ``tok`` / ``pos`` / ``len`` are [B] device tensors, so one captured step serves every token."""
+    slab. ``tok`` / ``pos`` / ``len`` are [B] device tensors, so one captured step serves every token. Over a
+    GroupedKVCache the same op gets the shared prefixes as well and the slabs hold the rows' own tokens only."""
 
     def __init__(self, model, cache: BatchKVCache):
         self.model, self.cache = model, cache
@@ -448,8 +488,13 @@ class BatchGraphDecoder:
 
     def _attend(self, li: int, qkv: torch.Tensor) -> torch.Tensor:  # the op appends each row's K/V itself
         nq, nkv, _ = _heads(self.model.config)
-        return ops.decode_attention_batched(qkv.contiguous(), self.cache.k[li], self.cache.v[li], self.len, nq, nkv,
-                                            window=self.windows[li])
+        c = self.cache
+        if c.pk is None:
+            return ops.decode_attention_batched(qkv.contiguous(), c.k[li], c.v[li], self.len, nq, nkv,
+                                                window=self.windows[li])
+        return ops.decode_attention_batched(qkv.contiguous(), c.k[li], c.v[li], self.len, nq, nkv,
+                                            window=self.windows[li], prefix_k=c.pk[li], prefix_v=c.pv[li],
+                                            prefix_lens=c.plens, group=c.group)
 
     def _step(self) -> torch.Tensor:
         return _logits(self.model, *_run_layers(self.model, self.tok, self.pos, self._attend))
@@ -571,7 +616,8 @@ def _decode_with_sampler(dec: BatchGraphDecoder, sm: BatchDeviceSampler, prompts
 def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eos_token_id: Optional[int] = None,
                   temperature: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
                   seed: Optional[int] = None, use_graph: Optional[bool] = None,
-                  device_sampling: Optional[bool] = None) -> Tuple[List[List[int]], Optional[List[List[float]]]]:
+                  device_sampling: Optional[bool] = None,
+                  num_generations: int = 1) -> Tuple[List[List[int]], Optional[List[List[float]]]]:
     """Sampled completions for reinforcement learning: ``(tokens, logps)``, row b drawn with ``seed + b`` and ending at
     its EOS (included) or at ``max_new_tokens``. With ``top_k == 0`` every token is a draw from softmax(penalised
     logits / temperature) over the WHOLE vocabulary and ``logps[b][i]`` is its log-probability under that distribution;
@@ -579,10 +625,20 @@ def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eo
     ``device_sampling=False``) the host loop draws with ``multinomial``. With ``top_k >= 1`` (clamped to the vocabulary)
     the device sampler draws from the top k (above 64: the threshold sampler, whose tokens for a seed are not the host
     loop's) and ``logps`` is None (a truncated behaviour policy has no full-vocabulary ratio).
+    ``num_generations=G > 1`` draws G completions of every prompt: the result has ``len(prompts) * G`` rows,
+    prompt-major, with the contract of passing every prompt G times (row b: ``seed + b``, its own history and EOS). On
+    the HIP path, for a model without a sliding window, the prompts are then prefilled once each and their K/V kept
+    once (``GroupedKVCache``), and every decode step reads a prompt once for its G rows; elsewhere the prompts are
+    simply repeated. The two round differently in the last bits of the attention output.
     The model's ``training`` flag is restored on return."""
     was_training = model.training
     model.eval()
     try:
+        G = int(num_generations)
+        if G < 1:
+            raise ValueError(f"num_generations must be >= 1, got {num_generations}")
+        unique = prompts
+        prompts = [p for p in unique for _ in range(G)]
         B = len(prompts)
         if B == 0:
             return [], ([] if not top_k else None)
@@ -596,9 +652,14 @@ def rollout_batch(model, prompts: List[List[int]], max_new_tokens: int = 256, eo
         dev = model.model.embed_tokens.device
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev,
-                             model.model.embed_tokens.dtype)
-        logits = prefill_batch(model, prompts, cache)
+        dt = model.model.embed_tokens.dtype
+        if G > 1 and _hip_decode(model, model.model.embed_tokens) and not any(_windows(model)):
+            cache = GroupedKVCache(model.config, len(unique), G, max(len(p) for p in unique), max_new_tokens + 1, dev,
+                                   dt)
+            logits = prefill_grouped(model, unique, cache)
+        else:
+            cache = BatchKVCache(model.config, B, max(len(p) for p in prompts) + max_new_tokens + 1, dev, dt)
+            logits = prefill_batch(model, prompts, cache)
         gpu_path = _hip_decode(model, logits)
         graph = gpu_path if use_graph is None else (use_graph and gpu_path)
         dec = BatchGraphDecoder(model, cache)

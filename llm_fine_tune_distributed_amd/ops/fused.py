@@ -1933,17 +1933,39 @@ def decode_attention(q, kcache, vcache, cache_len, n_q, n_kv, scale=None, window
     return torch.einsum("grs,sgd->grd", att.softmax(-1), vcache[lo:L].float()).reshape(-1).to(q.dtype)
 
 
-def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None, window=0):
+def decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, scale=None, window=0, prefix_k=None, prefix_v=None,
+                             prefix_lens=None, group=1):
     """One decode step of B sequences. ``qkv`` [B, (n_q + 2 n_kv) * D] is the step's post-RoPE projection,
     ``kcache`` / ``vcache`` [B, S_max, n_kv, D] one slab per sequence, ``lens`` [B] int32 the live length of each
     sequence INCLUDING the token being decoded. Row b's K/V are appended at ``cache[b, lens[b] - 1]`` (a length
     outside (0, S_max] skips the row), then row b attends over ``cache[b, :lens[b]]`` (with a sliding ``window``
     W > 0 over its last W rows, ``cache[b, max(0, lens[b] - W):lens[b]]``). Returns [B, n_q * D].
     The HIP kernels are built for head_dim 128 (csrc/decode_attention.hip) and 64 (csrc/decode_attention_d64.hip: MFMA
-    kernels, no sliding window); other head dims decode in torch, as they do in forward_cached."""
+    kernels, no sliding window); other head dims decode in torch, as they do in forward_cached.
+
+    With a prefix the rows come in groups of ``group`` that share one prompt: ``prefix_k`` / ``prefix_v``
+    [B / group, P_max, n_kv, D] hold the prompts' K/V once, ``prefix_lens`` [B / group] int32 their lengths, and the
+    caches only the rows' own tokens. ``lens`` keeps its meaning, so row b's own length is ``lens[b] -
+    prefix_lens[b // group]``: its K/V go to own row ``own - 1`` and it attends over ``prefix[b // group,
+    :prefix_lens]`` plus ``cache[b, :own]``. On the HIP path the prefix is streamed once per group against all
+    ``group * n_q / n_kv`` queries (csrc/decode_attention_d64.hip, head_dim 64 and 128; no sliding window)."""
     B = qkv.shape[0]
     D = qkv.shape[1] // (n_q + 2 * n_kv)
     window = _window(window, True)
+    prefix = (prefix_k, prefix_v, prefix_lens)
+    if any(p is not None for p in prefix) or group != 1:
+        if any(p is None for p in prefix):
+            raise ValueError("decode_attention_batched: prefix_k, prefix_v, prefix_lens and group go together")
+        if window:
+            raise ValueError("decode_attention_batched: no sliding window together with a prefix")
+        if group < 1 or B % group or prefix_k.shape[0] != B // group:
+            raise ValueError(f"decode_attention_batched: B = {B} rows are not {prefix_k.shape[0]} groups of {group}")
+        if _ext.use_hip(qkv):
+            scale = scale if scale is not None else 1.0 / math.sqrt(D)
+            return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale), 0,
+                                                       prefix_k, prefix_v, prefix_lens, int(group))
+        return ref.decode_attention_prefixed(qkv, kcache, vcache, lens, n_q, n_kv, scale, prefix_k, prefix_v,
+                                             prefix_lens, int(group))
     if _ext.use_hip(qkv) and D in (64, 128):
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
         return _ext.ops().decode_attention_batched(qkv, kcache, vcache, lens, n_q, n_kv, float(scale), window)

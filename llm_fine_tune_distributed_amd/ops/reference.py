@@ -155,6 +155,36 @@ def attention(qkv: torch.Tensor, n_q: int, n_kv: int, head_dim: int, cu_seqlens:
     return out.view(M, n_q * head_dim)
 
 
+def decode_attention_prefixed(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, lens: torch.Tensor,
+                              n_q: int, n_kv: int, scale: Optional[float], prefix_k: torch.Tensor,
+                              prefix_v: torch.Tensor, prefix_lens: torch.Tensor, group: int) -> torch.Tensor:
+    """One decode step of B = n_groups * group rows that share their group's prefix (ops.decode_attention_batched with
+    a prefix): row b appends its K/V at own row ``own - 1`` of ``kcache`` / ``vcache`` [B, S_own, n_kv, D], ``own =
+    lens[b] - prefix_lens[b // group]`` (``prefix_lens`` clamped to [0, P_max]; ``own`` outside (0, S_own] skips the
+    append and the own keys), and attends over ``prefix[b // group, :prefix_lens]`` followed by ``cache[b, :own]``:
+    fp32 softmax over the concatenated keys, one rounding. A row with no key at all gives zeros."""
+    B = qkv.shape[0]
+    D = qkv.shape[1] // (n_q + 2 * n_kv)
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    out = torch.zeros(B, n_q * D, dtype=qkv.dtype, device=qkv.device)
+    sown, pmax = kcache.shape[1], prefix_k.shape[1]
+    pl = prefix_lens.clamp(0, pmax).tolist()
+    for b, L in enumerate(lens.tolist()):
+        P = pl[b // group]
+        own = L - P if 0 < L - P <= sown else 0
+        if own:
+            kcache[b, own - 1] = qkv[b, n_q * D:(n_q + n_kv) * D].view(n_kv, D)
+            vcache[b, own - 1] = qkv[b, (n_q + n_kv) * D:].view(n_kv, D)
+        if P + own == 0:
+            continue
+        K = torch.cat([prefix_k[b // group, :P], kcache[b, :own]]).float()
+        V = torch.cat([prefix_v[b // group, :P], vcache[b, :own]]).float()
+        qg = qkv[b, :n_q * D].float().view(n_kv, n_q // n_kv, D)
+        att = torch.einsum("grd,sgd->grs", qg, K) * scale
+        out[b] = torch.einsum("grs,sgd->grd", att.softmax(-1), V).reshape(-1).to(qkv.dtype)
+    return out
+
+
 def _at_temperature(lf: torch.Tensor, temperature: float) -> torch.Tensor:
     """x / tau as the kernel forms it: one fp32 product with the fp32 value of 1 / tau (tau 1: x itself)."""
     if float(temperature) == 1.0:

@@ -416,6 +416,9 @@ class GRPOConfig(SFTConfig):
     reward_weights: Optional[List[float]] = None
     mask_truncated_completions: bool = False
     importance_sampling_level: str = "token"
+    # rollouts keep and read a prompt's K/V once for its num_generations rows (inference.rollout_batch with
+    # num_generations): same seeds and row order, attention rounded in another order than with the prompts repeated
+    rollout_shared_prompt: bool = False
     metric_for_best_model: Optional[str] = "eval_reward"
     greater_is_better: Optional[bool] = True
 

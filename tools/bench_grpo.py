@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--host-rollouts", type=int, default=0, help="also time this many host-loop rollouts of one micro-batch")
+    ap.add_argument("--shared-prompt", action="store_true",
+                    help="GRPOConfig.rollout_shared_prompt: a prompt's K/V kept and read once for its generations")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "outputs", "bench_grpo"))
     a = ap.parse_args()
 
@@ -60,7 +62,8 @@ def main():
     args = GRPOConfig(output_dir=a.out_dir, per_device_train_batch_size=a.micro, gradient_accumulation_steps=ga,
                       num_generations=a.generations, max_prompt_length=a.prompt, max_completion_length=a.new,
                       temperature=a.temperature, learning_rate=1e-6, max_grad_norm=1.0, gradient_checkpointing=False,
-                      jsonl_log=False, logging_steps=0, save_strategy="no", gemm_tuning=False)
+                      jsonl_log=False, logging_steps=0, save_strategy="no", gemm_tuning=False,
+                      rollout_shared_prompt=a.shared_prompt)
     trainer = GRPOTrainer(model=model, reward_funcs=low_share, args=args, train_dataset=ds)
     trainer._eos = None  # full-length completions: a fixed token count per step
     it = iter(trainer.get_train_dataloader())
@@ -90,6 +93,7 @@ def main():
     tokens = total * (a.prompt + a.new)
     rec = {"bench": "grpo", "model": a.model, "prompts_per_step": a.prompts, "generations": a.generations,
            "micro_batches": ga, "prompt_tokens": a.prompt, "new_tokens": a.new, "tokens_per_step": tokens,
+           "rollout_shared_prompt": a.shared_prompt,
            "steps": a.steps, "warmup": a.warmup, "rollout_ms_per_step": round(roll / a.steps * 1e3, 2),
            "update_ms_per_step": round(upd / a.steps * 1e3, 2),
            "rollout_new_tokens_per_sec": round(total * a.new * a.steps / roll, 1),
